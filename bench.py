@@ -2,6 +2,7 @@
 """Benchmark of the per-frame hot path on MI355X; prints ONE JSON line (rank 0).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --spp 4]
+                    [--dump-outputs DIR] [--full]
 
 A step is one full frame of BASELINE config 3 on the reference's default procedural scene and
 camera: per-frame two-level LBVH rebuild (kernel.cu:330-331), the path tracer at 4 spp
@@ -15,9 +16,19 @@ against the oracle: pipelined frames (the denoise/post chain of frame f on a sec
 beside the trace kernels of frame f+1, the LBVH build + camera rays of frame f+1 on a third
 beside the trace tails of frame f; --no-pipeline for serial frames).  Every frame's full work
 is inside the timed region: the last frame's deferred denoise is issued and waited for before
-the closing device sync.  After timing, rank 0 re-renders the same frame sequence serially in a
-fresh single-GPU context and compares the last frame bit for bit (--no-self-check skips it); a
-mismatch exits non-zero.
+the closing device sync.
+
+A plain run sets up, warms up, times the K frames and prints the headline line (metric, value,
+ms_per_step, fps, rays per frame).  --dump-outputs DIR then also writes what the last timed frame
+left for the caller as float32 DIR/<name>.npy: rgba8 (the displayed frame), hdr (the denoised HDR
+colour, half4 widened) and exposure (the auto-exposure state); an array above its share of 62 MB is
+a fixed, seeded sample of its pixels.  The scene, camera, sky and textures are procedural and the
+frames deterministic, so two builds run with the same arguments can be compared file for file.
+
+Everything else runs only with --full: the self-check (rank 0 re-renders the same frame sequence
+serially in a fresh single-GPU context and compares the last frame bit for bit; --no-self-check
+skips it; a mismatch exits non-zero), the per-kernel roofline below, the side measurements
+(--no-extras skips them) and the CPU baseline (--no-cpu-baseline skips it).
 
 N ranks (torch.distributed.run, one per GPU): each rank rebuilds the BVH, path traces its rows
 of the frame (16-row blocks dealt round-robin), the G-buffer blocks each rank's denoise reads are
@@ -58,7 +69,7 @@ for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md (spec peak)
+HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md (spec peak)
 L2_PEAK_GBS = 34500.0   # MI355X_MICROARCH.md, L2 (per XCD) section: aggregate L2 bandwidth
 # vector-instruction issue: a wave's f32 VALU instruction holds its SIMD 4 cycles (8 for the
 # transcendentals; MI355X_MICROARCH.md, 'vector-instruction ISSUE cost'); 256 CUs x 4 SIMDs at the
@@ -134,9 +145,16 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-stage, terrain and 1M-triangle side measurements")
-    ap.add_argument("--no-self-check", action="store_true", help="skip the serial re-render of the timed sequence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's outputs (rgba8, hdr, exposure) as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run the self-check, the per-kernel roofline, the side "
+                         "measurements and the CPU baseline (a plain run prints the headline figures only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the per-stage, terrain and 1M-triangle side measurements")
+    ap.add_argument("--no-self-check", action="store_true",
+                    help="with --full: skip the serial re-render of the timed sequence")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="gloo: rehearse the multi-rank path with ranks sharing a GPU (not a measurement)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -146,7 +164,10 @@ def parse():
     ap.add_argument("--extras-child", action="store_true", help=argparse.SUPPRESS)  # side legs, own process
     ap.add_argument("--check-file", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--check-frames", type=int, default=0, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def host_threads():
@@ -503,6 +524,25 @@ def self_check(rtx, W, H, S, tmp, last, final):
     return dict(same, frames=last, against="serial single-GPU re-render of frames 1..%d" % last, ok=all(same.values()))
 
 
+DUMP_BUDGET_BYTES = 62 * 10 ** 6  # of all dumped arrays together (float32)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, final):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last frame, as float32
+    .npy files: rgba8 [pixels, 4] (0..255), hdr [pixels, 4] (RENDER_COLOR, half4 widened exactly),
+    exposure [4].  A pixel array above its share of the budget is cut to a sorted sample of its pixels drawn
+    with a fixed seed, so the sample depends on the frame size alone."""
+    os.makedirs(path, exist_ok=True)
+    px = {"rgba8": final["rgba"].reshape(-1, 4), "hdr": final["color"].view(np.float16).reshape(-1, 4)}
+    keep = DUMP_BUDGET_BYTES // len(px) // 16  # pixels per array: 4 channels x 4 bytes each
+    for k, a in px.items():
+        if len(a) > keep:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    np.save(os.path.join(path, "exposure.npy"), final["exposure"].view(np.float32).copy())
+
+
 def extras_child(args):
     """The side measurements, in a process of their own (so that the timed process's rocprofv3 stats
     hold only the timed workload): traversal under load (the terrain camera, pipelined, with its own
@@ -718,7 +758,7 @@ def main():
     rays = rt.ray_count()
     last = args.warmup + args.steps
     final = None
-    if rank == 0 and not args.no_self_check:
+    if rank == 0 and (args.dump_outputs or (args.full and not args.no_self_check)):
         final = dict(rgba=rt.download("RGBA8", np.uint8).copy(), color=rt.get_buffer("RENDER_COLOR").copy(),
                      exposure=rt.download("EXPOSURE", np.uint8).copy())
     if world > 1:
@@ -758,6 +798,15 @@ def main():
         "fps": round(1000.0 / ms_per_step, 2),
         "rays_per_frame": int(rays // args.steps),
     }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, final)
+    if not args.full:  # the headline figures only
+        rt.cleanup()
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel roofline over this rank's strip: work counters of one detail launch (after the
     # timed frames), kernel durations from the timed frames' events; the denoise kernels' gating
@@ -840,11 +889,11 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_extras:
         cf = None
-        if final is not None:
+        if final is not None and not args.no_self_check:
             cf = os.path.join(tmp, "final.npz")
             np.savez(cf, **final)
         result.update(run_extras(args, cf, last))
-    elif final is not None:
+    elif final is not None and not args.no_self_check:
         result["self_check"] = self_check(rtx, W, H, S, tmp, last, final)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(W, H, S)

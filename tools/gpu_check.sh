@@ -20,7 +20,7 @@ if [[ $WHAT == tests || $WHAT == all ]]; then
 fi
 if [[ $WHAT == bench || $WHAT == all ]]; then
   step bench
-  timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
 fi
 step done

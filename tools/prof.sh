@@ -5,8 +5,8 @@
 # <outdir>/pmc.json.
 #   tools/prof.sh <outdir> stats|pmc|both|trace [python args...]
 # e.g. tools/prof.sh gpurun_out/dn both tools/probe.py denoise --n 10
-#      tools/prof.sh gpurun_out/b stats bench.py --gpus 1 --steps 20 --warmup 5
-#      tools/prof.sh gpurun_out/tl trace bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-self-check
+#      tools/prof.sh out/b stats bench.py --full --gpus 1 --steps 20 --warmup 5
+#      tools/prof.sh out/tl trace bench.py --steps 10 --warmup 3
 # PASSES overrides the counter groups (';'-separated); KEY / WORKLOAD label pmc.json (bench.py reads
 # the committed copy when its workload_key matches, e.g. KEY=1920x1080x4).  trace: a kernel trace and
 # its pipelined-frame timeline (tools/timeline.py) in <outdir>/timeline.txt.
