@@ -50,7 +50,9 @@ typedef struct rt_context rt_context;
  * the shade kernel never / beside the lean bounce kernels / always), specShadePerCu, specTracePerCu,
  * specChain (-1: by queue 3's length); the denoise list passes: dnSplit (0 / 1 / 2: two threads per
  * pixel never / in synchronous frames / always; default 0), dnFold (bool, default false: the last
- * a-trous pass over list 1 only).  [debug] (fault
+ * a-trous pass over list 1 only); resumeSplit (0 / 1 / 2: resume<3> of the four-kernel
+ * bounce chain as one kernel / split into the shading list's kernel and a lean pass / the lean pass on
+ * a stream of its own in pipelined one-GPU frames).  [debug] (fault
  * injection, tests): bvhSkipPublish, bvhSkipPublishBuilds, bvhWaitMs.  The library reads no
  * environment variables. */
 int rt_create(int screen_width, int screen_height, const char* config_toml, rt_context** out);
@@ -450,7 +452,9 @@ enum rt_array_name {
                                     kernel, [14,15] the shade kernel (inline glossy traces),
                                     [16,17] the step-3 and [18,19] the step-4 queue tracers,
                                     diffuse events of [20] the shade and [21] the resume<3> kernel,
-                                    [22] camera rays settled by the scene cull (no traversal) */
+                                    [22] camera rays settled by the scene cull (no traversal);
+                                    [23] entries of the step-3 queue's shading list (bounce rays that
+                                    hit a triangle; 0 when resume<3> runs unsplit or as the fused chain) */
     RT_ARR_PT_Q3_ORIGINS = 33,   /* float4[cap] step-3 queue rays of the last launch: origin xyz, pixel bits */
     RT_ARR_PT_Q3_DIRS = 34,      /* float4[cap] direction xyz, flags bits ([0] of RT_ARR_PT_QUEUE are valid) */
     RT_ARR_PT_Q4_ORIGINS = 35,   /* float4[cap] step-4 queue, same layout ([1] valid) */

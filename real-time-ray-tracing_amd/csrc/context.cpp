@@ -346,6 +346,8 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
         t.specTracePerCu = rttoml::find_or_int(doc, "tuning", "specTracePerCu", 2);
         t.dnSplit = rttoml::find_or_int(doc, "tuning", "dnSplit", 0);
         t.dnFold = rttoml::find_or_int(doc, "tuning", "dnFold", 0) != 0;
+        t.resumeSplit = rttoml::find_or_int(doc, "tuning", "resumeSplit", t.resumeSplit);
+        t.resumeSplit = t.resumeSplit < 0 ? 0 : t.resumeSplit > 2 ? 2 : t.resumeSplit;
     }
     if (ctx->screenW <= 0 || ctx->screenH <= 0 || ctx->screenW > 16384 || ctx->screenH > 16384 || ctx->spp < 1 ||
         ctx->spp > 64 || ctx->chunkDim < 1 || ctx->chunkDim > 8 ||
@@ -506,9 +508,11 @@ void rt_destroy(rt_context* ctx) {
                          ctx->bvhFree[0], ctx->bvhFree[1]})
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kGbSets; ++k)
-        for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k]})
+        for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k],
+                             ctx->leanTraced[k], ctx->leanDone[k]})
             if (e) (void)hipEventDestroy(e);
     if (ctx->sideStream) (void)hipStreamDestroy(ctx->sideStream);
+    if (ctx->leanStream) (void)hipStreamDestroy(ctx->leanStream);
     if (ctx->ownPostStream) (void)hipStreamDestroy(ctx->ownPostStream);
     for (void* p : ctx->allocations) (void)hipFree(p);
     if (ctx->fr.q3Host) (void)hipHostFree(ctx->fr.q3Host);

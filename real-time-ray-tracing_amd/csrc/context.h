@@ -129,6 +129,7 @@ struct FrameResources {
     float* camHitErr[kGbSets] = {};
     float4* camPathL[kGbSets] = {};
     uint32_t* camPending[kGbSets] = {};
+    uint32_t* camShade3[kGbSets] = {};  // queue 3's shading list (PtWorkspace::shade3; [tuning] resumeSplit)
     int lastSlot = 0;                  // slot of the last path trace (RT_ARR_PT_Q*)
     // queue 3's length after the last serial path trace, copied to pinned host memory behind it
     // (the fused chain's on/off choice for serial frames)
@@ -232,6 +233,10 @@ struct rt_context {
         int specTracePerCu = 2; // ... this frame's bounce chain / queue-3 tracer at so many workgroups per CU (0: as usual)
         int dnSplit = 0;        // the denoise list passes at two threads per pixel: 0 never, 1 synchronous frames, 2 always
         bool dnFold = false;    // the last a-trous pass over list 1 only, its other tiles written by the first
+        // resume<3> of the four-kernel bounce chain: 0 one kernel over the queue in order, 1 split into the
+        // shading list's kernel and a lean pass on the same stream, 2 the lean pass on a stream of its own
+        // in pipelined one-GPU frames (elsewhere as 1); the default is the fastest measured
+        int resumeSplit = 2;
     } tune;
 
     std::string err;
@@ -257,6 +262,8 @@ struct rt_context {
     hipStream_t postStream = nullptr;  // optional: denoise + post run here (rt_set_post_stream)
     hipStream_t ownPostStream = nullptr;  // created by an asynchronous rt_draw_device (destroyed by rt_destroy)
     hipStream_t sideStream = nullptr;  // pipelining: LBVH build + camera rays of the next frame
+    hipStream_t leanStream = nullptr;  // pipelining: the forked lean pass of the split resume<3> (resumeSplit 2)
+    hipEvent_t leanTraced[kGbSets] = {}, leanDone[kGbSets] = {};  // its fork and join, per set as restDone
     hipEvent_t ptDone[kGbSets] = {}, postDone[kGbSets] = {}, overlapEv = nullptr;
     rt_collective_fn hook = nullptr;     // multi-GPU strip-local denoise exchanges (rt_set_collective_hook)
     void* hookArg = nullptr;

@@ -325,6 +325,8 @@ int sync_streams(rt_context* ctx, bool report) {
     }
     if (ctx->sideStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->sideStream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // joined into the context stream before each resolve; on its own only after a failed launch
+    if (ctx->leanStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->leanStream));
     if (ctx->postStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->postStream));
     poll_q3(ctx);
     // camera rays a synchronous draw traced ahead are kept only up to the next draw: any call that
@@ -480,6 +482,7 @@ int rt_frame_init(rt_context* ctx) {
         ALLOC(ws.hitRec, cap * 16);
         ALLOC(ws.hitErr, cap * 4);
         ALLOC(ws.pathL, cap * 16);
+        if (ctx->tune.resumeSplit > 0) ALLOC(fr.camShade3[0], cap * 4);
         ALLOC(ws.pending, (size_t)ctx->renderW * ctx->stripRows * 4);
         ALLOC(ws.surface, (size_t)ctx->renderW * ctx->stripRows * 4);
         ALLOC(fr.camCount[0], kWsCounterWords * 4);
@@ -651,6 +654,7 @@ int alloc_ws_slot(rt_context* ctx, int k, bool queues) {
         ALLOC(fr.camHitErr[k], cap * 4);
         ALLOC(fr.camPathL[k], cap * 16);
         ALLOC(fr.camPending[k], strip * 4);
+        if (ctx->tune.resumeSplit > 0) ALLOC(fr.camShade3[k], cap * 4);
     }
 #undef ALLOC
     return rc;
@@ -723,6 +727,9 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.ws.hitErr = fr.camHitErr[qs];
     p.ws.pathL = fr.camPathL[qs];
     p.ws.pending = fr.camPending[qs];
+    p.ws.hitRec4 = p.ws.hitRec;  // one stream: queue 3's records are dead once queue 4 is traced
+    p.ws.hitErr4 = p.ws.hitErr;
+    p.ws.shade3 = fr.camShade3[qs];  // null: resume<3> unsplit ([tuning] resumeSplit = 0)
     {  // material table (init.cu:215-251): only mirror / glass ids make steps 1-2 trace
         const int m = ctx->materialOverride;
         p.ws.glossy = m >= 0 && (m == 1 || m == 5 || m >= 10);
@@ -754,6 +761,7 @@ bool spec_matches(const PathTraceParams& a, const PathTraceParams& b) {
         q->ws.chain = 0;
         q->ws.q3HostOut = nullptr;
         q->ws.q3Tag = 0;
+        q->ws.shade3 = nullptr;  // read from trace<3> on
     }
     return memcmp(&x, &y, sizeof x) == 0;
 }
@@ -814,6 +822,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         if (ctx->tune.specTracePerCu > 0) p.ws.traceBlocks = fr.ws.cus * (uint32_t)ctx->tune.specTracePerCu;
     }
     fr.lastChain = p.ws.chain && !p.ws.glossy && !p.ws.microfacet;  // as rtk_launch_pt_rest decides
+    if (fr.lastChain || p.ws.glossy) p.ws.shade3 = nullptr;  // the fused chain and the glossy tables keep no shading list
     if (with_detail) {  // per-pixel counters: everything in order on the context stream
         if (ctx->postStream && (rc = sync_streams(ctx)) != RT_OK) return rc;
         HIP_TRY(ctx, hipMemsetAsync(fr.rays, 0, (size_t)ctx->renderW * ctx->renderH * 4, ctx->stream));
@@ -884,11 +893,22 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         p.ws.q3Tag = ++fr.q3Tag;
     }
     PtLaunchHook shook{spec_hook, ctx};
-    if (shadeSide) HIP_TRY(ctx, rtk_launch_pt_rest_after_shade(&p, ctx->stream, ctx->ptMarks, &hook));
-    else if (reuseShade) HIP_TRY(ctx, rtk_launch_pt_rest_after_shade(&p, ctx->stream, ctx->ptMarks, &shook));
+    // The lean pass of the split resume<3> on its own stream (resumeSplit 2): pipelined one-GPU frames
+    // only; serial frames, detail launches and strip ranks keep one stream.  Queue 4's hit records then
+    // go to this set's camera-hit planes, which nothing reads once the shade kernel is done (the set's
+    // next camera kernel waits for restDone[g]).
+    PtLeanFork lean{ctx->leanStream, ctx->leanTraced[g], ctx->leanDone[g]};
+    const bool fork = side && p.ws.shade3 && ctx->leanStream && ctx->stripCount == 1;
+    if (fork) {
+        p.ws.hitRec4 = p.ws.hit0Rec;
+        p.ws.hitErr4 = p.ws.hit0Err;
+    }
+    const PtLeanFork* lf = fork ? &lean : nullptr;
+    if (shadeSide) HIP_TRY(ctx, rtk_launch_pt_rest_after_shade(&p, ctx->stream, ctx->ptMarks, &hook, lf));
+    else if (reuseShade) HIP_TRY(ctx, rtk_launch_pt_rest_after_shade(&p, ctx->stream, ctx->ptMarks, &shook, lf));
     else {
         const PtLaunchHook* h = ctx->postStream ? &hook : spec_on(ctx) && !with_detail ? &shook : nullptr;
-        HIP_TRY(ctx, rtk_launch_pt_rest(&p, ctx->stream, ctx->ptMarks, h));
+        HIP_TRY(ctx, rtk_launch_pt_rest(&p, ctx->stream, ctx->ptMarks, h, lf));
     }
     // pending only once the launches that store it are enqueued: a failed launch leaves the next
     // serial frame to ask again instead of freezing the chain choice
@@ -1377,6 +1397,10 @@ int rt_set_post_stream(rt_context* ctx, void* stream) {
     for (int k = 0; k < kGbSets; ++k) {
         if (!ctx->camDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->camDone[k], hipEventDisableTiming));
         if (!ctx->restDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->restDone[k], hipEventDisableTiming));
+        if (ctx->tune.resumeSplit == 2) {
+            if (!ctx->leanTraced[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->leanTraced[k], hipEventDisableTiming));
+            if (!ctx->leanDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->leanDone[k], hipEventDisableTiming));
+        }
         fr.camInFlight[k] = false;
     }
     ctx->bvhInFlight[0] = ctx->bvhInFlight[1] = false;
@@ -1394,6 +1418,8 @@ int rt_set_post_stream(rt_context* ctx, void* stream) {
     ctx->cameraAfter = ctx->stripCount == 1 ? 0 : ctx->stripCount == 2 ? 2 : ctx->stripCount < 8 ? 3 : 1;
     if (ctx->tune.overlapAfter >= 0) ctx->overlapAfter = ctx->tune.overlapAfter;  // [tuning] A/B aids
     if (ctx->tune.cameraAfter >= 0) ctx->cameraAfter = ctx->tune.cameraAfter;
+    if (ctx->tune.resumeSplit == 2 && !ctx->leanStream && (rc = rt_create_stream(ctx, &ctx->leanStream, false)) != RT_OK)
+        return rc;
     ctx->postStream = (hipStream_t)stream;
     return RT_OK;
 }

@@ -66,6 +66,15 @@ struct HistCamera { float pos[3], left[3], up[3], dir[3]; };  // HistoryCamera (
 // has matType MAT_SKY), so the queue tracer ends those traversals at their first hit.
 constexpr uint32_t kQShadowFlag = 1u;
 
+// Whether the resume of a queue-3 entry can reach the diffuse interaction D1: only a bounce ray
+// (not a shadow ray) that hit a triangle gets a diffuse material (update_material); every other
+// entry ends with its hit applied.  flags: the entry's rayD.w bits; hitIdxBits: the hit record's
+// triangle index bits (negative: a miss).  One predicate for the tracer's shading list and the two
+// resume kernels, so that every entry is resumed exactly once.
+__host__ __device__ inline bool q3_shades(uint32_t flags, uint32_t hitIdxBits) {
+    return (flags & kQShadowFlag) == 0u && (int32_t)hitIdxBits >= 0;
+}
+
 struct PtQueue {
     float4* rayO;
     float4* rayD;
@@ -79,11 +88,12 @@ struct PtQueue {
 // per-kernel roofline (bench.py): node visits and triangle tests of the camera kernel, the
 // shade kernel's inline (glossy) traces and the two queue tracers; diffuse events of the shade
 // and resume<3> kernels; [22] camera rays the scene cull settled without a traversal
+// [23]: length of the queue-3 shading list (PtWorkspace::shade3), counted in every launch that keeps one
 enum PtCounter : int { kCntQ3 = 0, kCntQ4 = 1, kCntFetch3 = 2, kCntFetch4 = 3, kCntPending = 4, kCntResume3 = 5,
                        kCntResume4 = 6, kCntResolve = 7, kCntMaxIter3 = 8, kCntMaxIter4 = 9, kCntError = 10,
                        kCntSurface = 11, kCntVisCam = 12, kCntTstCam = 13, kCntVisShade = 14, kCntTstShade = 15,
                        kCntVisQ3 = 16, kCntTstQ3 = 17, kCntVisQ4 = 18, kCntTstQ4 = 19, kCntDiffShade = 20,
-                       kCntDiffRes3 = 21, kCntCulledCam = 22, kCntSlots = 23 };
+                       kCntDiffRes3 = 21, kCntCulledCam = 22, kCntShade3 = 23, kCntSlots = 24 };
 // counters | fetch: [2][8 parts x 16] queue-tracer fetch counters, then [8 parts x 16] the shade
 // kernel's batch claims (k_pt_shade0), all zeroed together
 constexpr int kWsCounterWords = 64 + 3 * 8 * 16;
@@ -95,6 +105,14 @@ struct PtWorkspace {
     PtQueue q3, q4;             // rays deferred at step 3 / step 4 of PathTrace's sequence
     float4* hitRec;             // [cap] (t, triangle index bits, u, v) of the closest hit
     float* hitErr;              // [cap] its errorT
+    // queue 4's hit records: hitRec / hitErr again, or planes of their own when queue-3 entries are
+    // still being resumed while queue 4 is traced (the forked lean pass, rtk_launch_pt_rest)
+    float4* hitRec4 = nullptr;
+    float* hitErr4 = nullptr;
+    // optional [cap]: queue-3 entries whose resume may shade (q3_shades), appended by k_trace_queue<3>,
+    // counters[kCntShade3] long.  Set: resume<3> runs as k_pt_resume3_shade over this list plus
+    // k_pt_resume3_lean over the other entries
+    uint32_t* shade3 = nullptr;
     float4* pathL;              // [rows*W*spp] per-sample radiance of pixels resolved late
     uint32_t* pending;          // [rows*W] pixel (strip-local) | first deferred sample << 26
     uint32_t* surface;          // [rows*W] strip-local pixels with a sample that hit geometry
@@ -268,6 +286,14 @@ struct PtLaunchHook {
     hipError_t (*fn)(void* arg, int kernel);  // after each kernel is enqueued (1 = shade, 2 = trace<3>, ...)
     void* arg;
 };
+// Optional fork of the split resume<3>'s lean pass (ws.shade3 set): it runs on `stream` once trace<3>
+// is done (`traced`, recorded on the launch stream), beside the shading pass, trace<4> and
+// resume<4>; the launch stream waits for `done` before the resolve kernel.  ws.hitRec4 / hitErr4
+// must then not alias ws.hitRec / hitErr.
+struct PtLeanFork {
+    hipStream_t stream;
+    hipEvent_t traced, done;
+};
 // The camera kernel (writes the hit records, the surface list and the sky pixels' G-buffer) and
 // the rest (shade .. resolve) can go to different streams: the frame pipeline runs the camera
 // rays of frame f+1 beside the trace tails of frame f (frame.cpp).  marks: 2 * kPtKernels events,
@@ -275,7 +301,7 @@ struct PtLaunchHook {
 // (k = 0 by the camera launcher, 1..6 by the rest; rt_time_path_trace_kernels, rt_time_frame_kernels).
 extern "C" hipError_t rtk_launch_pt_camera(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks);
 extern "C" hipError_t rtk_launch_pt_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks,
-                                         const PtLaunchHook* hook);
+                                         const PtLaunchHook* hook, const PtLeanFork* fork);
 // The shade kernel alone (kernel 1, marks[2] / marks[3]), for a caller that runs it behind the
 // camera kernel on another stream; rtk_launch_pt_rest_after_shade then enqueues trace<3> ..
 // resolve and calls the hook for kernel 1 first, with nothing enqueued for it.
@@ -285,6 +311,6 @@ extern "C" hipError_t rtk_launch_pt_shade(const PathTraceParams* p, hipStream_t 
 // dst null: only the zeroing
 extern "C" hipError_t rtk_fold_ray_counts(unsigned long long* dst, unsigned long long* src, hipStream_t stream);
 extern "C" hipError_t rtk_launch_pt_rest_after_shade(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks,
-                                                     const PtLaunchHook* hook);
+                                                     const PtLaunchHook* hook, const PtLeanFork* fork);
 extern "C" int rtk_trace_queue_blocks_per_cu();
 extern "C" hipError_t rtk_launch_trace_queue(const PathTraceParams* p, int step, hipStream_t stream);

@@ -856,13 +856,11 @@ RT_DEV int resume_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
     return needs_trace(v.rs) ? 4 : 5;
 }
 
-// Entry i of queue kStep (3 or 4): reloads the sample's state, applies the hit the tracer found
-// (t, triangle index bits, u, v; errorT) and runs the rest of its sequence.  Returns 4 when the
-// I4 ray must be traced (kStep == 3 only), else 5 (the sample is complete).  kGlossy: the material
-// table holds mirror or glass.
-template <int kStep, bool kMF, bool kGlossy>
-RT_DEV int resume_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
-                        PathVars& v, uint32_t& p, uint32_t& s) {
+// Entry i of a bounce queue: reloads the sample's state and turns the hit the tracer found (t,
+// triangle index bits, u, v; errorT) into the HitInfo of its intersection.  Shared by resume_entry
+// and the lean pass of the split resume<3>.
+RT_DEV void reload_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
+                         PathVars& v, uint32_t& p, uint32_t& s, HitInfo& h) {
     const PathTraceParams& P = c.P;
     const float4 o = q.rayO[i], d = q.rayD[i], s0 = q.st0[i], s1 = q.st1[i], s2 = q.st2[i];
     p = __float_as_uint(o.w);
@@ -888,8 +886,17 @@ RT_DEV int resume_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint3
     rs.centerRaydir = f3(0.0f);  // read by D0 only
     rs.matId = 0;
     rs.matType = MAT_SKY;
-    HitInfo h;
     finalize_hit(sc, rs.orig, rs.dir, hr.x, (int)__float_as_uint(hr.y), hr.z, hr.w, herr, h);
+}
+
+// Entry i of queue kStep (3 or 4): reloads the sample's state, applies the hit the tracer found
+// and runs the rest of its sequence.  Returns 4 when the I4 ray must be traced (kStep == 3 only),
+// else 5 (the sample is complete).  kGlossy: the material table holds mirror or glass.
+template <int kStep, bool kMF, bool kGlossy>
+RT_DEV int resume_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
+                        PathVars& v, uint32_t& p, uint32_t& s) {
+    HitInfo h;
+    reload_entry(c, q, sc, i, hr, herr, v, p, s, h);
     if constexpr (kGlossy && kStep == 3) return run_path<0, kMF>(c, v, kStep, &h, sc, nullptr);
     else return resume_diffuse<kStep, kMF>(c, v, h);
 }
@@ -931,7 +938,9 @@ __global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_
         PathVars v;
         int kd = 5;
         uint32_t p = 0, s = 0;
-        if (active) kd = resume_entry<kStep, kMF, kGlossy>(c, q, sc, i, P.ws.hitRec[i], P.ws.hitErr[i], v, p, s);
+        if (active)
+            kd = resume_entry<kStep, kMF, kGlossy>(c, q, sc, i, (kStep == 3 ? P.ws.hitRec : P.ws.hitRec4)[i],
+                                                   (kStep == 3 ? P.ws.hitErr : P.ws.hitErr4)[i], v, p, s);
         const uint32_t slot = wave_append(kd == 4, &P.ws.counters[kCntQ4]);
         if (active) {
             if (kd < 5) {  // kStep == 3 only: the I4 ray
@@ -951,6 +960,83 @@ __global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_
     }
     if (kStep == 3 && P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays);
+}
+
+// The split resume<3> (ws.shade3 set; default materials or the microfacet one): of the queue-3
+// entries only a bounce ray that hit a triangle can reach the diffuse interaction D1 (q3_shades),
+// 5-15 % of them, scattered through the queue; taken in queue order nearly every wave of
+// k_pt_resume<3> paid D1's path for a handful of lanes.  k_trace_queue<3> lists those entries, and
+//   k_pt_resume3_shade  runs k_pt_resume<3>'s loop body over the list, one listed entry per lane;
+//   k_pt_resume3_lean   runs over the whole queue, skips the listed entries and ends the others:
+//                       reload, apply_hit, finish.  No tables in LDS, no blue-noise value read.
+// Per entry the code is k_pt_resume<3>'s, and every entry is resumed by exactly one of the two.
+template <bool kMF>
+__global__ __launch_bounds__(256, 3) void k_pt_resume3_shade(PathTraceParams P) {
+    __shared__ uint32_t sob[256];
+    __shared__ unsigned long long wgRays[4];
+    __shared__ __align__(16) float sSkyTree[kSkyTreeNodes];
+    __shared__ __align__(16) float sSunTree[kSunTreeNodes];
+    const uint32_t n = P.ws.counters[kCntShade3];
+    if (blockIdx.x * 256u >= n) return;  // past the list: leave before staging the tables; no ray counted
+    const int tid = threadIdx.x;
+    bn_stage_sobol(P.bluenoise, sob, tid, 256);
+    stage_cdf_trees(P, sSkyTree, sSunTree, tid, 256);
+    __syncthreads();
+    const SceneView sc = scene_of(P);
+    uint32_t rays = 0, rsD = 0;
+#pragma unroll 1
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {  // block-uniform
+        const uint32_t li = base + (uint32_t)tid;
+        const bool active = li < n;
+        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
+        c.skyTree = sSkyTree;
+        c.sunTree = sSunTree;
+        PathVars v;
+        int kd = 5;
+        uint32_t p = 0, s = 0;
+        if (active) {
+            const uint32_t i = P.ws.shade3[li];
+            kd = resume_entry<3, kMF, false>(c, P.ws.q3, sc, i, P.ws.hitRec[i], P.ws.hitErr[i], v, p, s);
+        }
+        const uint32_t slot = wave_append(kd == 4, &P.ws.counters[kCntQ4]);
+        if (active) {
+            if (kd < 5) {  // the I4 ray
+                ++c.rays;
+                enqueue(P.ws.q4, slot, v, p, s);
+            } else {
+                store_path_L(c, v, p, s);
+            }
+            if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
+            if (P.statsOut) {
+                if (c.rays) atomicAdd(&P.statsOut[p].x, c.rays);
+                if (c.diffuse) atomicAdd(&P.statsOut[p].w, c.diffuse);
+                rsD += c.diffuse;
+            }
+            rays += c.rays;
+        }
+    }
+    if (P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
+    add_rays(P, wgRays, rays);
+}
+
+__global__ __launch_bounds__(256) void k_pt_resume3_lean(PathTraceParams P) {
+    const uint32_t n = P.ws.counters[kCntQ3];
+    const SceneView sc = scene_of(P);
+#pragma unroll 1
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const float4 hr = P.ws.hitRec[i];
+        if (q3_shades(__float_as_uint(P.ws.q3.rayD[i].w), __float_as_uint(hr.y))) continue;  // k_pt_resume3_shade's
+        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), nullptr, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
+        PathVars v;
+        uint32_t p = 0, s = 0;
+        HitInfo h;
+        reload_entry(c, P.ws.q3, sc, i, hr, P.ws.hitErr[i], v, p, s, h);
+        apply_hit(P, v.rs, h);
+        // D1 would act on this entry: cannot happen (update_material gives a diffuse material only
+        // to a bounce ray's triangle hit, which q3_shades lists); flag it, the sample ends here
+        if (!(v.rs.hitLight || !v.rs.isDiffuse || v.rs.isOccluded)) atomicAdd(&P.ws.counters[kCntError], 1u);
+        store_path_L(c, v, p, s);
+    }
 }
 
 constexpr int kChainRanges = 32;  // queue-3 reserves a wave records before it resumes them
@@ -1267,7 +1353,7 @@ void launch_shade(const PathTraceParams* p, hipStream_t stream) {
 }
 
 hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks, const PtLaunchHook* hook,
-                       bool withShade);
+                       const PtLeanFork* fork, bool withShade);
 }  // namespace
 
 extern "C" hipError_t rtk_launch_pt_shade(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks) {
@@ -1279,18 +1365,18 @@ extern "C" hipError_t rtk_launch_pt_shade(const PathTraceParams* p, hipStream_t 
 }
 
 extern "C" hipError_t rtk_launch_pt_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks,
-                                         const PtLaunchHook* hook) {
-    return launch_rest(p, stream, marks, hook, true);
+                                         const PtLaunchHook* hook, const PtLeanFork* fork) {
+    return launch_rest(p, stream, marks, hook, fork, true);
 }
 
 extern "C" hipError_t rtk_launch_pt_rest_after_shade(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks,
-                                                     const PtLaunchHook* hook) {
-    return launch_rest(p, stream, marks, hook, false);
+                                                     const PtLaunchHook* hook, const PtLeanFork* fork) {
+    return launch_rest(p, stream, marks, hook, fork, false);
 }
 
 namespace {
 hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks, const PtLaunchHook* hook,
-                       bool withShade) {
+                       const PtLeanFork* fork, bool withShade) {
     hipError_t e = hipSuccess;  // the counters were zeroed before the camera kernel (rtk_launch_pt_camera)
     int k = 1;  // kernel 1 = shade; marks[2k] / marks[2k + 1] bracket kernel k on this stream
     // a null entry: that kernel is not bracketed (rt_frame_marks_begin's kernel mask)
@@ -1323,15 +1409,32 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
             if ((e = end()) != hipSuccess || (e = begin()) != hipSuccess) return e;
     } else {
         if ((e = rtk_launch_trace_queue(p, 3, stream)) != hipSuccess || (e = end()) != hipSuccess) return e;
+        // the lean pass of the split resume<3>, forked: it needs trace<3>'s records only, and nothing
+        // before the resolve kernel needs it (queue 4's hit records then have planes of their own)
+        const bool split = p->ws.shade3 != nullptr && !p->ws.glossy;
+        const bool forked = split && fork && fork->stream;
+        if (forked) {
+            if (p->ws.hitRec4 == p->ws.hitRec || p->ws.hitErr4 == p->ws.hitErr) return hipErrorInvalidValue;
+            if ((e = hipEventRecord(fork->traced, stream)) != hipSuccess) return e;
+            if ((e = hipStreamWaitEvent(fork->stream, fork->traced, 0)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_pt_resume3_lean, pg, pb, 0, fork->stream, *p);
+            if ((e = hipEventRecord(fork->done, fork->stream)) != hipSuccess) return e;
+        }
         if ((e = begin()) != hipSuccess) return e;
-        if (p->ws.microfacet) hipLaunchKernelGGL((k_pt_resume<3, true, false>), pg, pb, 0, stream, *p);
+        if (split) {  // the shading list first: it feeds queue 4
+            if (p->ws.microfacet) hipLaunchKernelGGL(k_pt_resume3_shade<true>, pg, pb, 0, stream, *p);
+            else hipLaunchKernelGGL(k_pt_resume3_shade<false>, pg, pb, 0, stream, *p);
+            if (!forked) hipLaunchKernelGGL(k_pt_resume3_lean, pg, pb, 0, stream, *p);
+        } else if (p->ws.microfacet) hipLaunchKernelGGL((k_pt_resume<3, true, false>), pg, pb, 0, stream, *p);
         else if (p->ws.glossy) hipLaunchKernelGGL((k_pt_resume<3, false, true>), pg, pb, 0, stream, *p);
         else hipLaunchKernelGGL((k_pt_resume<3, false, false>), pg, pb, 0, stream, *p);
         if ((e = end()) != hipSuccess || (e = begin()) != hipSuccess) return e;
         if ((e = rtk_launch_trace_queue(p, 4, stream)) != hipSuccess || (e = end()) != hipSuccess) return e;
         if ((e = begin()) != hipSuccess) return e;
         hipLaunchKernelGGL((k_pt_resume<4, false, false>), pg, pb, 0, stream, *p);  // step 4 shades nothing
-        if ((e = end()) != hipSuccess || (e = begin()) != hipSuccess) return e;
+        if ((e = end()) != hipSuccess) return e;
+        if (forked && (e = hipStreamWaitEvent(stream, fork->done, 0)) != hipSuccess) return e;  // its pathL stores
+        if ((e = begin()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_pt_resolve, dim3(p->ws.persistBlocks), dim3(256), 0, stream, *p);
     if ((e = end()) != hipSuccess) return e;

@@ -30,10 +30,25 @@ constexpr uint32_t kTrace3Short = 1u << 20;  // queue-3 length below which trace
 #endif
 constexpr bool kLeafBatch = RTX_LEAF_BATCH != 0;  // ablation: -DRTX_LEAF_BATCH=0
 
+// A wave's pending entries of the shading list (PtWorkspace::shade3) go out n <= 64 at a time: one
+// atomic per flush, and the wave waits for its return once per ~64 listed entries.  (One atomic per
+// loop trip that finished a listed ray, ~47 k on one address with every wave waiting for each of
+// its own, stretched trace<3> 248 -> 380 us in the pipeline.)  Wave-uniform call; the wave's LDS
+// accesses execute in order, the fences keep the compiler from reordering them.
+RT_DEV void flush_shade_list(const PathTraceParams& P, uint32_t* shl, uint32_t n, int lane) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    uint32_t base = 0u;
+    if (lane == 0) base = atomicAdd(&P.ws.counters[kCntShade3], n);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if ((uint32_t)lane < n) P.ws.shade3[base + (uint32_t)lane] = shl[lane];
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
 // kStats: the launch keeps per-pixel statistics (P.statsOut), so the traversal counts visits and tests
 template <int kStep, bool kStats>
 __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) {
     __shared__ uint2 stk[17 * kTraceBlock];  // 16 entries + the dead slot trav_step stores above the top
+    __shared__ uint32_t shadeList[kStep == 3 ? kTraceBlock : 1];  // per wave: 64 pending shading-list entries
     // The tracers' waves issue at the denoise kernels' priority (DN_PRIO), above the next frame's
     // camera waves: in a pipelined frame the context stream binds (bench.py binding_stream), and its
     // queue tracers' time is their longest rays' dependent iterations, which stretch when the SIMD
@@ -62,6 +77,8 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
 
     bool active = false, exhausted = false, occlusion = false;
     uint32_t idx = 0, accV = 0, accT = 0;
+    uint32_t* const shl = shadeList + (kStep == 3 ? (tid & ~63) : 0);  // this wave's
+    uint32_t nList = 0;  // wave-uniform
     TravRay r;
     TravState s;
     TravRec rec;  // the record the lane's next iteration processes
@@ -98,6 +115,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
         // leaf batching (a wave in the tail has few lanes left, and its iteration latency is the
         // kernel's tail).  Each ray's steps are unchanged.
         const bool tail = f.resLo == f.resHi && f.drained == (1u << kParts) - 1u;
+        bool fin = false;  // this lane finished its ray in this trip
         if (tail || !kLeafBatch ? active : trav_lane_steps(active, s)) {
             bool done;
             do {  // two steps per trip: the loop's refill / exec-mask bookkeeping once per two
@@ -108,8 +126,9 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
                            (occlusion && s.hitIdx >= 0);
             } while (tail && !done);
             if (done) {
-                P.ws.hitRec[idx] = make_float4(s.t, __uint_as_float((uint32_t)s.hitIdx), s.hitU, s.hitV);
-                P.ws.hitErr[idx] = s.hitErrT;
+                (kStep == 3 ? P.ws.hitRec : P.ws.hitRec4)[idx] =
+                    make_float4(s.t, __uint_as_float((uint32_t)s.hitIdx), s.hitU, s.hitV);
+                (kStep == 3 ? P.ws.hitErr : P.ws.hitErr4)[idx] = s.hitErrT;
                 if (P.ws.itersOut) P.ws.itersOut[idx] = s.iters;
                 if (P.statsOut) {
                     const uint32_t p = __float_as_uint(q.rayO[idx].w);
@@ -120,9 +139,25 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
                     accT += s.tests;
                 }
                 active = false;
+                fin = true;
+            }
+        }
+        // the entries whose resume may shade go to the shading list (split resume<3>); wave-uniform flow
+        if (kStep == 3 && P.ws.shade3) {
+            const unsigned long long m = __ballot(fin && q3_shades(occlusion ? kQShadowFlag : 0u, (uint32_t)s.hitIdx));
+            if (m != 0ull) {
+                const uint32_t k = (uint32_t)__popcll(m);
+                if (nList + k > 64u) {
+                    flush_shade_list(P, shl, nList, lane);
+                    nList = 0u;
+                }
+                if ((m >> lane) & 1ull)
+                    shl[nList + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = idx;
+                nList += k;
             }
         }
     }
+    if (kStep == 3 && P.ws.shade3 && nList) flush_shade_list(P, shl, nList, lane);
     if (P.statsOut) {  // every lane left the loop together (the wave-uniform break above)
         uint32_t v = accV, t = accT;
 #pragma unroll

@@ -1,0 +1,171 @@
+"""The split resume<3> ([tuning] resumeSplit): k_trace_queue<3> lists the queue-3
+entries whose resume can shade (a bounce ray that hit a triangle), k_pt_resume3_shade runs over that
+list and k_pt_resume3_lean over the other entries, in pipelined one-GPU frames on a stream of its
+own (resumeSplit = 2).  Per entry the code is the unsplit kernel's, so every comparison here is
+bit for bit: against the unsplit kernel (resumeSplit = 0), the CPU oracle and serial frames.
+"""
+import numpy as np
+import pytest
+
+from test_gpu_pathtrace import assert_gbuffers_equal, gpu_gbuffers, terrain_camera
+
+pytestmark = pytest.mark.gpu
+
+FRAME = 3
+DT = 16.667
+
+
+@pytest.fixture(scope="module")
+def sky_tex(oracle):
+    return oracle.sky(), oracle.textures()
+
+
+def cameras(rtx, oracle, w, h, kind):
+    if kind == "terrain":
+        return terrain_camera(rtx, oracle, w, h)
+    if kind == "sky":  # straight up from above the terrain: no camera ray hits, queue 3 stays empty
+        return terrain_camera(rtx, oracle, w, h, pitch=1.5)
+    return oracle.default_camera(w, h), None
+
+
+def trace(rtx, tmp_path, w, h, spp, split, rcam=None, extra=""):
+    """One detail launch of frame FRAME as four lean kernels (chain off): G-buffers, RAYS, counters."""
+    cfg = rtx.write_config(str(tmp_path / ("s%d.toml" % split)), w, h, spp=spp, extra=extra,
+                           tuning={"chain": "off", "resumeSplit": split})
+    rt = rtx.RayTracer(w, h, cfg).init()
+    if rcam is not None:
+        rt.camera = rcam
+    rt.build_bvh()
+    rt.path_trace(FRAME, detail=True)
+    rt.sync()
+    g = gpu_gbuffers(rt, w, h)
+    q = rt.download("PT_QUEUE", np.uint32).copy()
+    rays = rt.ray_count()
+    rt.cleanup()
+    return g, q, rays
+
+
+@pytest.mark.parametrize("cam_kind", ["terrain", "default", "sky"])
+@pytest.mark.parametrize("spp", [4, 1])
+@pytest.mark.parametrize("w,h", [(100, 60), (192, 108)])
+def test_split_matches_unsplit_and_oracle(rtx, oracle, tmp_path, default_scene, sky_tex, w, h, spp, cam_kind):
+    ocam, rcam = cameras(rtx, oracle, w, h, cam_kind)
+    ref, q0, rays0 = trace(rtx, tmp_path, w, h, spp, 0, rcam)
+    assert q0[10] == 0  # kCntError
+    assert q0[23] == 0  # no shading list without the split
+    if cam_kind == "sky":
+        assert q0[0] == 0  # queue 3 is empty
+    elif cam_kind == "terrain":
+        assert q0[0] > 256  # more than one workgroup's entries
+    else:
+        assert q0[0] > 0
+    for split in (1, 2):
+        g, q, rays = trace(rtx, tmp_path, w, h, spp, split, rcam)
+        assert_gbuffers_equal(g, ref)
+        assert rays == rays0
+        assert q[10] == 0
+        for k in (0, 1, 4, 11, 20, 21):  # queue lengths, pending and surface pixels, diffuse events
+            assert q[k] == q0[k], k
+        assert q[23] <= q[0]
+        if (w, h) == (192, 108) and cam_kind == "terrain":
+            s, tex = sky_tex
+            o = oracle.pathtrace(default_scene["bvh"], w, h, frame_num=FRAME, spp=spp, cam=ocam, sky_out=s, tex=tex)
+            assert_gbuffers_equal(g, o)
+            assert rays == int(o["rays"].sum())
+
+
+def test_shading_list_counts_the_d1_events(rtx, oracle, tmp_path):
+    """Default materials: every triangle is Lambertian (update_material gives id 3, or 6 past the
+    triangle count, both LAMBERTIAN in the reference table), so a listed entry (a bounce ray's
+    triangle hit) is a D1 event and the reverse: the list's length equals resume<3>'s diffuse count."""
+    w, h = 192, 108
+    _, rcam = terrain_camera(rtx, oracle, w, h)
+    for split in (1, 2):
+        _, q, _ = trace(rtx, tmp_path, w, h, 4, split, rcam)
+        assert q[21] > 0
+        assert q[23] == q[21], (q[23], q[21])
+        assert q[23] < q[0]  # shadow rays and misses are not listed
+
+
+def test_emissive_override_finishes_without_shading(rtx, oracle, tmp_path, default_scene, sky_tex):
+    """materialOverride = 0 (emissive): no entry may shade.  The override covers every triangle, so a
+    camera ray's hit already ends its path (hitLight) and nothing reaches queue 3: the shading list
+    and both resume kernels run over empty ranges."""
+    s, tex = sky_tex
+    w, h = 100, 60
+    ocam, rcam = terrain_camera(rtx, oracle, w, h)
+    extra = "materialOverride = 0\n"
+    ref, q0, _ = trace(rtx, tmp_path, w, h, 4, 0, rcam, extra)
+    o = oracle.pathtrace(default_scene["bvh"], w, h, frame_num=FRAME, spp=4, cam=ocam, sky_out=s, tex=tex,
+                         material_override=0)
+    assert_gbuffers_equal(ref, o)
+    for split in (1, 2):
+        g, q, _ = trace(rtx, tmp_path, w, h, 4, split, rcam, extra)
+        assert_gbuffers_equal(g, ref)
+        assert_gbuffers_equal(g, o)
+        assert q[10] == 0 and q[21] == 0  # no error, no D1 event
+        assert q[23] == q0[0] == 0
+
+
+def pipeline(rtx, tmp_path, pipelined, split, per_frame, frames=8, w=192, h=108):
+    """`frames` frames through FramePipeline with the camera turning: every frame's RGBA8
+    (per_frame: a host read per frame) and the final history."""
+    import torch
+
+    from rtx.frames import FramePipeline
+
+    cfg = rtx.write_config(str(tmp_path / ("p%d%d%d.toml" % (pipelined, split, per_frame))), w, h, spp=4,
+                           tuning={"resumeSplit": split})
+    rt = rtx.RayTracer(w, h, cfg).init()
+    rt.set_delta_time(DT)
+    prev = torch.cuda.current_stream(0)
+    fp = FramePipeline(rt, torch.device("cuda", 0), pipelined=pipelined)
+    images = []
+    try:
+        cam0 = rt.camera
+        for f in range(1, frames + 1):
+            c = rt.camera
+            c.yaw = cam0.yaw + 0.02 * f
+            rt.camera = c
+            fp.frame(f)
+            if per_frame:
+                images.append(rt.download("RGBA8", np.uint8).copy())
+        fp.finish()
+        out = dict(rgba=rt.download("RGBA8", np.uint8).copy(), hist=rt.get_buffer("HISTORY_COLOR").copy(),
+                   acc=rt.get_buffer("ACCUMULATION").copy(), expo=rt.download("EXPOSURE", np.uint8).copy())
+    finally:
+        rt.cleanup()
+        torch.cuda.set_stream(prev)
+    return out, images
+
+
+@pytest.fixture(scope="module")
+def serial_frames(rtx, tmp_path_factory):
+    return pipeline(rtx, tmp_path_factory.mktemp("serial"), False, 0, True)
+
+
+def test_pipelined_forked_lean_pass_matches_serial(rtx, tmp_path, serial_frames):
+    ref, ref_imgs = serial_frames
+    got, _ = pipeline(rtx, tmp_path, True, 2, False)  # frames in flight: no host read between them
+    for k in ref:
+        assert np.array_equal(ref[k], got[k]), k
+    got, imgs = pipeline(rtx, tmp_path, True, 2, True)
+    assert len(imgs) == len(ref_imgs) == 8
+    for f, (a, b) in enumerate(zip(ref_imgs, imgs)):
+        assert np.array_equal(a, b), "frame %d" % (f + 1)
+    for k in ref:
+        assert np.array_equal(ref[k], got[k]), k
+
+
+def test_two_strips_match_serial(rtx, tmp_path, serial_frames, monkeypatch):
+    """Two strip ranks on one GPU (tests/test_gpu_multirank_pipeline.py's helper, whose configs take
+    RTX_TUNING) with resumeSplit = 2: both ranks equal the one-rank pipelined run, which equals the
+    serial frames."""
+    from test_gpu_multirank_pipeline import run
+
+    monkeypatch.setenv("RTX_TUNING", "resumeSplit=2")
+    run(tmp_path, 2, (192, 108), 8, "rs", False)
+    one = np.load(tmp_path / "rsr0_of1.npz")
+    ref, _ = serial_frames
+    for k in ("rgba", "hist", "acc", "expo"):
+        assert np.array_equal(one[k], ref[k]), k
