@@ -821,8 +821,9 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         // (synchronous draw 0.985 -> 0.972 ms at 2 per CU against 3)
         if (ctx->tune.specTracePerCu > 0) p.ws.traceBlocks = fr.ws.cus * (uint32_t)ctx->tune.specTracePerCu;
     }
-    fr.lastChain = p.ws.chain && !p.ws.glossy && !p.ws.microfacet;  // as rtk_launch_pt_rest decides
-    if (fr.lastChain || p.ws.glossy) p.ws.shade3 = nullptr;  // the fused chain and the glossy tables keep no shading list
+    const PtBouncePlan plan = pt_bounce_plan(p.ws);
+    fr.lastChain = plan == PtBouncePlan::chain;
+    if (plan != PtBouncePlan::split) p.ws.shade3 = nullptr;  // only the split resume<3> keeps a shading list
     if (with_detail) {  // per-pixel counters: everything in order on the context stream
         if (ctx->postStream && (rc = sync_streams(ctx)) != RT_OK) return rc;
         HIP_TRY(ctx, hipMemsetAsync(fr.rays, 0, (size_t)ctx->renderW * ctx->renderH * 4, ctx->stream));
@@ -898,7 +899,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     // go to this set's camera-hit planes, which nothing reads once the shade kernel is done (the set's
     // next camera kernel waits for restDone[g]).
     PtLeanFork lean{ctx->leanStream, ctx->leanTraced[g], ctx->leanDone[g]};
-    const bool fork = side && p.ws.shade3 && ctx->leanStream && ctx->stripCount == 1;
+    const bool fork = side && plan == PtBouncePlan::split && ctx->leanStream && ctx->stripCount == 1;
     if (fork) {
         p.ws.hitRec4 = p.ws.hit0Rec;
         p.ws.hitErr4 = p.ws.hit0Err;

@@ -141,6 +141,17 @@ struct PtWorkspace {
     int countersZeroed = 0;
 };
 
+// How a launch runs the bounces behind the shade kernel (host side; the one statement of the rule):
+//   chain    k_pt_chain: trace<3> .. resume<4> in one launch, for the default materials only
+//   split    four kernels, resume<3> as k_pt_resume3_shade over ws.shade3 plus k_pt_resume3_lean;
+//            the glossy tables keep no shading list
+//   unsplit  four kernels, k_pt_resume<3> over queue 3 in order
+enum class PtBouncePlan { chain, split, unsplit };
+inline PtBouncePlan pt_bounce_plan(const PtWorkspace& ws) {
+    if (ws.chain && !ws.glossy && !ws.microfacet) return PtBouncePlan::chain;
+    return ws.shade3 && !ws.glossy ? PtBouncePlan::split : PtBouncePlan::unsplit;
+}
+
 // The frame's traced-ray count is kept as partial sums in kRayCounterSlots slots 128 B apart
 // (one atomic per workgroup into slot blockId % slots; the host adds them): a device-scope
 // atomic on one address serialises at the memory side, and one per workgroup on a single

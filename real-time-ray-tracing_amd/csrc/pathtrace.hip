@@ -54,6 +54,13 @@ struct PathCtx {
     const float* sunTree = nullptr;
 };
 
+// a lane's context before its pixel and sample are known.  sob, skyTree, sunTree: the workgroup's
+// LDS tables (the chain passes the heaps in global memory); null where the caller's path reads
+// no blue-noise value or samples no light
+RT_DEV PathCtx path_ctx(const PathTraceParams& P, const uint32_t* sob, const float* skyTree, const float* sunTree) {
+    return PathCtx{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u, skyTree, sunTree};
+}
+
 // copy the light-CDF probe heaps into LDS (all threads of the workgroup; caller syncs)
 RT_DEV void stage_cdf_trees(const PathTraceParams& P, float* sky, float* sun, int tid, int nthreads) {
     for (int i = tid; i < kSkyTreeNodes / 4; i += nthreads) reinterpret_cast<float4*>(sky)[i] = reinterpret_cast<const float4*>(P.skyTree)[i];
@@ -498,7 +505,7 @@ __global__ __launch_bounds__(256, kOneRound ? 6 : 4) void k_pt_camera(PathTraceP
     const uint32_t pl = (uint32_t)yl * P.width + (uint32_t)x;
     const size_t plane = (size_t)P.rows * P.width;
     const SceneView sc = scene_of(P);
-    PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
+    PathCtx c = path_ctx(P, sob, nullptr, nullptr);  // a miss samples no light
     if (active) c.bp = bn_pixel(P.bluenoise, x, y);
     const int rounds = kOneRound ? 1 : ((int)P.spp + nSW - 1) / nSW;
     F3 L = f3(0.0f), A = f3(0.0f);  // folding thread (sw == 0): running sums of an all-sky pixel
@@ -714,9 +721,7 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
         const int x = (int)(pl % P.width), yl = (int)(pl / P.width);
         const int y = (int)row_of(P.y0, P.nStrips, P.strip, (uint32_t)yl);
         const uint32_t p = (uint32_t)y * P.width + (uint32_t)x;
-        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
-        c.skyTree = sSkyTree;
-        c.sunTree = sSunTree;
+        PathCtx c = path_ctx(P, sob, sSkyTree, sSunTree);
         float coneSpread = 0.0f;
         F3 centerDir = f3(0.0f);
         if (active) {  // per-pixel invariants of the sample loop
@@ -909,114 +914,96 @@ RT_DEV void store_path_L(const PathCtx& c, const PathVars& v, uint32_t p, uint32
     P.ws.pathL[(size_t)pl * P.spp + s] = make_float4(Ls.x, Ls.y, Ls.z, 0.0f);
 }
 
-// Resumes the samples of queue kStep (3 or 4) once k_trace_queue has written their hits.
-template <int kStep, bool kMF, bool kGlossy>
-__global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_resume(PathTraceParams P) {
+// What follows resume_entry on a lane: the I4 ray (kd == 4) is appended to queue 4, any other sample
+// is complete and stores its radiance; then the lane's per-pixel ray and diffuse-event counts.
+// Called by every lane of the wave (wave_append); an idle lane passes active = false, kd = 5.
+// Adds the lane's counts to the caller's rays and rsD (the latter in detail launches only) and
+// returns its queue-4 slot.
+RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd, uint32_t p, uint32_t s, uint32_t& rays,
+                             uint32_t& rsD) {
+    const PathTraceParams& P = c.P;
+    const uint32_t slot = wave_append(kd == 4, &P.ws.counters[kCntQ4]);
+    if (active) {
+        if (kd < 5) {  // out of step 3 only
+            ++c.rays;
+            enqueue(P.ws.q4, slot, v, p, s);
+        } else {
+            store_path_L(c, v, p, s);
+        }
+        if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
+        if (P.statsOut) {
+            if (c.rays) atomicAdd(&P.statsOut[p].x, c.rays);
+            if (c.diffuse) atomicAdd(&P.statsOut[p].w, c.diffuse);
+            rsD += c.diffuse;
+        }
+        rays += c.rays;
+    }
+    return slot;
+}
+
+// One workgroup of a resume kernel: the samples of queue kStep (3 or 4) once k_trace_queue has
+// written their hits.  kListed (queue 3, no mirror or glass): not the queue in order but its
+// entries on the shading list ws.shade3, one listed entry per lane.
+template <int kStep, bool kMF, bool kGlossy, bool kListed>
+RT_DEV void resume_queue(const PathTraceParams& P) {
+    static_assert(!kListed || (kStep == 3 && !kGlossy), "the shading list is queue 3's, kept without glossy tables");
     __shared__ uint32_t sob[256];
     __shared__ unsigned long long wgRays[4];
     // step 4 ends the path before any diffuse interaction: no light sampling there
     __shared__ __align__(16) float sSkyTree[kStep == 3 ? kSkyTreeNodes : 4];
     __shared__ __align__(16) float sSunTree[kStep == 3 ? kSunTreeNodes : 4];
-    const uint32_t n = P.ws.counters[kStep == 3 ? kCntQ3 : kCntQ4];
-    // a workgroup past the queue (queue 4 holds a few thousand entries against a grid sized for
-    // queue 3) leaves before staging its tables; block-uniform, no ray counted
+    const uint32_t n = P.ws.counters[kListed ? kCntShade3 : kStep == 3 ? kCntQ3 : kCntQ4];
+    // a workgroup past the end (queue 4 holds a few thousand entries, the shading list 5-15 % of
+    // queue 3, against a grid sized for queue 3) leaves before staging its tables; block-uniform,
+    // no ray counted
     if (blockIdx.x * 256u >= n) return;
     const int tid = threadIdx.x;
     bn_stage_sobol(P.bluenoise, sob, tid, 256);
     if (kStep == 3) stage_cdf_trees(P, sSkyTree, sSunTree, tid, 256);
     __syncthreads();
     const PtQueue& q = kStep == 3 ? P.ws.q3 : P.ws.q4;
-    const SceneView sc = scene_of(P);
-    uint32_t rays = 0, rsD = 0;
-#pragma unroll 1
-    for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {  // block-uniform
-        const uint32_t i = base + (uint32_t)tid;
-        const bool active = i < n;
-        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
-        c.skyTree = sSkyTree;
-        c.sunTree = sSunTree;
-        PathVars v;
-        int kd = 5;
-        uint32_t p = 0, s = 0;
-        if (active)
-            kd = resume_entry<kStep, kMF, kGlossy>(c, q, sc, i, (kStep == 3 ? P.ws.hitRec : P.ws.hitRec4)[i],
-                                                   (kStep == 3 ? P.ws.hitErr : P.ws.hitErr4)[i], v, p, s);
-        const uint32_t slot = wave_append(kd == 4, &P.ws.counters[kCntQ4]);
-        if (active) {
-            if (kd < 5) {  // kStep == 3 only: the I4 ray
-                ++c.rays;
-                enqueue(P.ws.q4, slot, v, p, s);
-            } else {
-                store_path_L(c, v, p, s);
-            }
-            if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
-            if (P.statsOut) {
-                if (c.rays) atomicAdd(&P.statsOut[p].x, c.rays);
-                if (c.diffuse) atomicAdd(&P.statsOut[p].w, c.diffuse);
-                rsD += c.diffuse;
-            }
-            rays += c.rays;
-        }
-    }
-    if (kStep == 3 && P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
-    add_rays(P, wgRays, rays);
-}
-
-// The split resume<3> (ws.shade3 set; default materials or the microfacet one): of the queue-3
-// entries only a bounce ray that hit a triangle can reach the diffuse interaction D1 (q3_shades),
-// 5-15 % of them, scattered through the queue; taken in queue order nearly every wave of
-// k_pt_resume<3> paid D1's path for a handful of lanes.  k_trace_queue<3> lists those entries, and
-//   k_pt_resume3_shade  runs k_pt_resume<3>'s loop body over the list, one listed entry per lane;
-//   k_pt_resume3_lean   runs over the whole queue, skips the listed entries and ends the others:
-//                       reload, apply_hit, finish.  No tables in LDS, no blue-noise value read.
-// Per entry the code is k_pt_resume<3>'s, and every entry is resumed by exactly one of the two.
-template <bool kMF>
-__global__ __launch_bounds__(256, 3) void k_pt_resume3_shade(PathTraceParams P) {
-    __shared__ uint32_t sob[256];
-    __shared__ unsigned long long wgRays[4];
-    __shared__ __align__(16) float sSkyTree[kSkyTreeNodes];
-    __shared__ __align__(16) float sSunTree[kSunTreeNodes];
-    const uint32_t n = P.ws.counters[kCntShade3];
-    if (blockIdx.x * 256u >= n) return;  // past the list: leave before staging the tables; no ray counted
-    const int tid = threadIdx.x;
-    bn_stage_sobol(P.bluenoise, sob, tid, 256);
-    stage_cdf_trees(P, sSkyTree, sSunTree, tid, 256);
-    __syncthreads();
+    const float4* hitRec = kStep == 3 ? P.ws.hitRec : P.ws.hitRec4;
+    const float* hitErr = kStep == 3 ? P.ws.hitErr : P.ws.hitErr4;
     const SceneView sc = scene_of(P);
     uint32_t rays = 0, rsD = 0;
 #pragma unroll 1
     for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {  // block-uniform
         const uint32_t li = base + (uint32_t)tid;
         const bool active = li < n;
-        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
-        c.skyTree = sSkyTree;
-        c.sunTree = sSunTree;
+        PathCtx c = path_ctx(P, sob, sSkyTree, sSunTree);
         PathVars v;
         int kd = 5;
         uint32_t p = 0, s = 0;
         if (active) {
-            const uint32_t i = P.ws.shade3[li];
-            kd = resume_entry<3, kMF, false>(c, P.ws.q3, sc, i, P.ws.hitRec[i], P.ws.hitErr[i], v, p, s);
+            const uint32_t i = kListed ? P.ws.shade3[li] : li;
+            kd = resume_entry<kStep, kMF, kGlossy>(c, q, sc, i, hitRec[i], hitErr[i], v, p, s);
         }
-        const uint32_t slot = wave_append(kd == 4, &P.ws.counters[kCntQ4]);
-        if (active) {
-            if (kd < 5) {  // the I4 ray
-                ++c.rays;
-                enqueue(P.ws.q4, slot, v, p, s);
-            } else {
-                store_path_L(c, v, p, s);
-            }
-            if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
-            if (P.statsOut) {
-                if (c.rays) atomicAdd(&P.statsOut[p].x, c.rays);
-                if (c.diffuse) atomicAdd(&P.statsOut[p].w, c.diffuse);
-                rsD += c.diffuse;
-            }
-            rays += c.rays;
-        }
+        finish_entry(c, v, active, kd, p, s, rays, rsD);
     }
-    if (P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
+    if (kStep == 3 && P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays);
+}
+
+// Queue kStep taken in order: queue 4 always, queue 3 when it keeps no shading list.
+template <int kStep, bool kMF, bool kGlossy>
+__global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_resume(PathTraceParams P) {
+    resume_queue<kStep, kMF, kGlossy, false>(P);
+}
+
+// The split resume<3> (ws.shade3 set; default materials or the microfacet one): of the queue-3
+// entries only a bounce ray that hit a triangle can reach the diffuse interaction D1 (q3_shades),
+// 5-15 % of them, scattered through the queue; taken in queue order nearly every wave of
+// k_pt_resume<3> paid D1's path for a handful of lanes.  k_trace_queue<3> lists those entries, and
+//   k_pt_resume3_shade  is k_pt_resume<3> with another index source: resume_queue over the list,
+//                       one listed entry per lane, instead of over the queue in order;
+//   k_pt_resume3_lean   runs over the whole queue, skips the listed entries and ends the others:
+//                       reload, apply_hit, finish.  No tables in LDS, no blue-noise value read.
+// There is one body (resume_queue, which the chain's phase 2 shares from resume_entry on:
+// finish_entry); the lean loop below is what that body does for an entry D1 leaves alone.  Every
+// entry is resumed by exactly one of the two kernels.
+template <bool kMF>
+__global__ __launch_bounds__(256, 3) void k_pt_resume3_shade(PathTraceParams P) {
+    resume_queue<3, kMF, false, true>(P);
 }
 
 __global__ __launch_bounds__(256) void k_pt_resume3_lean(PathTraceParams P) {
@@ -1026,7 +1013,7 @@ __global__ __launch_bounds__(256) void k_pt_resume3_lean(PathTraceParams P) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const float4 hr = P.ws.hitRec[i];
         if (q3_shades(__float_as_uint(P.ws.q3.rayD[i].w), __float_as_uint(hr.y))) continue;  // k_pt_resume3_shade's
-        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), nullptr, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
+        PathCtx c = path_ctx(P, nullptr, nullptr, nullptr);
         PathVars v;
         uint32_t p = 0, s = 0;
         HitInfo h;
@@ -1058,7 +1045,7 @@ constexpr bool kChainStaticFirst = RTX_CHAIN_STATIC != 0;  // ablation: static f
 //            appends the I4 rays to queue 4 and to a per-wave slot list, and once 64 slots could
 //            overflow, or at the end, traces them one per lane and finishes them (resume<4>).
 //   repeat   when the reserve list was full before the queue drained.
-// Per sample the code is the one the separate kernels run (resume_entry, trav_step), so the
+// Per sample the code is the one the separate kernels run (resume_entry, finish_entry, trav_step), so the
 // G-buffers are identical.  The hit records a wave reads in phase 2 are ones its own lanes wrote
 // (a workgroup-scope fence orders them), so no record crosses workgroups inside the launch.
 template <bool kStats>
@@ -1086,7 +1073,7 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
     const uint32_t allParts = (1u << kParts) - 1u;
     Fetch f;
     fetch_init(f, n, gridDim.x * 4u, blockIdx.x * 4u + (uint32_t)w, kChainStaticFirst);
-    uint32_t rays = 0;
+    uint32_t rays = 0, rsD = 0;
 #pragma unroll 1
     while (true) {  // wave-uniform
         // ---- phase 1: trace queue-3 entries, recording the reserves taken
@@ -1158,9 +1145,7 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
         }
         // ---- phase 2: resume this wave's entries, trace and finish their I4 rays
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the hit records this wave wrote
-        PathCtx c{P, f3(P.sunDir[0], P.sunDir[1], P.sunDir[2]), sob, BnPixel{0u, 0u}, 0, 0u, 0u, 0u, 0u};
-        c.skyTree = P.skyTree;  // the light-CDF heaps from L2: LDS holds the traversal stacks
-        c.sunTree = P.sunTree;
+        PathCtx c = path_ctx(P, sob, P.skyTree, P.sunTree);  // the light-CDF heaps from L2: LDS holds the traversal stacks
         uint32_t ri = 0, nq4 = 0;
 #pragma unroll 1
         while (true) {
@@ -1221,32 +1206,15 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
             c.rays = 0;
             c.diffuse = 0;
             if (act) kd = resume_entry<3, false, false>(c, q, sc, i, P.ws.hitRec[i], P.ws.hitErr[i], v, p, smp);
-            const bool i4 = kd == 4;
-            const uint32_t slot = wave_append(i4, &P.ws.counters[kCntQ4]);
-            const unsigned long long m4 = __ballot(i4);
-            if (act) {
-                if (i4) {
-                    ++c.rays;
-                    enqueue(P.ws.q4, slot, v, p, smp);
-                    q4list[w][nq4 + lane_rank(m4)] = slot;
-                } else {
-                    store_path_L(c, v, p, smp);
-                }
-                if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
-                if (P.statsOut) {
-                    if (c.rays) atomicAdd(&P.statsOut[p].x, c.rays);
-                    if (c.diffuse) {
-                        atomicAdd(&P.statsOut[p].w, c.diffuse);
-                        atomicAdd(&P.ws.counters[kCntDiffRes3], c.diffuse);
-                    }
-                }
-                rays += c.rays;
-            }
+            const uint32_t slot = finish_entry(c, v, act, kd, p, smp, rays, rsD);
+            const unsigned long long m4 = __ballot(kd == 4);
+            if (kd == 4) q4list[w][nq4 + lane_rank(m4)] = slot;
             nq4 += (uint32_t)__popcll(m4);
             ++ri;
         }
         if (f.resLo == f.resHi && f.drained == allParts) break;  // queue 3 drained
     }
+    if (P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays, w);
 }
 
@@ -1391,53 +1359,59 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
         ++k;
         return hipSuccess;
     };
+    // one kernel slot: its begin mark, what it enqueues (possibly nothing), its end mark and the hook
+    auto stage = [&](auto launch) {
+        hipError_t se = begin();
+        if (se == hipSuccess) se = launch();
+        return se == hipSuccess ? end() : se;
+    };
     const dim3 pg(p->ws.persistBlocks), pb(256);
+    auto kernel = [&](void (*fn)(PathTraceParams), dim3 grid, hipStream_t s) {  // errors surface in hipGetLastError below
+        hipLaunchKernelGGL(fn, grid, pb, 0, s, *p);
+        return hipSuccess;
+    };
     if (withShade) {
-        if ((e = begin()) != hipSuccess) return e;
-        launch_shade(p, stream);
-        if ((e = end()) != hipSuccess) return e;
+        e = stage([&] { launch_shade(p, stream); return hipSuccess; });
     } else {  // enqueued by the caller on another stream: only the hook runs for kernel 1
-        if (hook && hook->fn && (e = hook->fn(hook->arg, k)) != hipSuccess) return e;
+        if (hook && hook->fn) e = hook->fn(hook->arg, k);
         ++k;
     }
-    if ((e = begin()) != hipSuccess) return e;
-    if (p->ws.chain && !p->ws.glossy && !p->ws.microfacet) {
+    if (e != hipSuccess) return e;
+    const PtBouncePlan plan = pt_bounce_plan(p->ws);
+    if (plan == PtBouncePlan::chain) {
         // kernel 2 = the fused bounce chain (trace<3> .. resume<4>); slots 3-5 stay empty, so the
         // hook's kernel numbers and the per-kernel timing slots keep their meaning
-        hipLaunchKernelGGL(p->statsOut ? k_pt_chain<true> : k_pt_chain<false>, dim3(p->ws.traceBlocks), pb, 0, stream, *p);
-        for (int j = 0; j < 4; ++j)
-            if ((e = end()) != hipSuccess || (e = begin()) != hipSuccess) return e;
+        e = stage([&] { return kernel(p->statsOut ? k_pt_chain<true> : k_pt_chain<false>, dim3(p->ws.traceBlocks), stream); });
+        for (int j = 3; j <= 5 && e == hipSuccess; ++j) e = stage([] { return hipSuccess; });
+        if (e != hipSuccess) return e;
     } else {
-        if ((e = rtk_launch_trace_queue(p, 3, stream)) != hipSuccess || (e = end()) != hipSuccess) return e;
+        if ((e = stage([&] { return rtk_launch_trace_queue(p, 3, stream); })) != hipSuccess) return e;
         // the lean pass of the split resume<3>, forked: it needs trace<3>'s records only, and nothing
         // before the resolve kernel needs it (queue 4's hit records then have planes of their own)
-        const bool split = p->ws.shade3 != nullptr && !p->ws.glossy;
+        const bool split = plan == PtBouncePlan::split;
         const bool forked = split && fork && fork->stream;
         if (forked) {
             if (p->ws.hitRec4 == p->ws.hitRec || p->ws.hitErr4 == p->ws.hitErr) return hipErrorInvalidValue;
             if ((e = hipEventRecord(fork->traced, stream)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(fork->stream, fork->traced, 0)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_pt_resume3_lean, pg, pb, 0, fork->stream, *p);
+            (void)kernel(k_pt_resume3_lean, pg, fork->stream);
             if ((e = hipEventRecord(fork->done, fork->stream)) != hipSuccess) return e;
         }
-        if ((e = begin()) != hipSuccess) return e;
-        if (split) {  // the shading list first: it feeds queue 4
-            if (p->ws.microfacet) hipLaunchKernelGGL(k_pt_resume3_shade<true>, pg, pb, 0, stream, *p);
-            else hipLaunchKernelGGL(k_pt_resume3_shade<false>, pg, pb, 0, stream, *p);
-            if (!forked) hipLaunchKernelGGL(k_pt_resume3_lean, pg, pb, 0, stream, *p);
-        } else if (p->ws.microfacet) hipLaunchKernelGGL((k_pt_resume<3, true, false>), pg, pb, 0, stream, *p);
-        else if (p->ws.glossy) hipLaunchKernelGGL((k_pt_resume<3, false, true>), pg, pb, 0, stream, *p);
-        else hipLaunchKernelGGL((k_pt_resume<3, false, false>), pg, pb, 0, stream, *p);
-        if ((e = end()) != hipSuccess || (e = begin()) != hipSuccess) return e;
-        if ((e = rtk_launch_trace_queue(p, 4, stream)) != hipSuccess || (e = end()) != hipSuccess) return e;
-        if ((e = begin()) != hipSuccess) return e;
-        hipLaunchKernelGGL((k_pt_resume<4, false, false>), pg, pb, 0, stream, *p);  // step 4 shades nothing
-        if ((e = end()) != hipSuccess) return e;
-        if (forked && (e = hipStreamWaitEvent(stream, fork->done, 0)) != hipSuccess) return e;  // its pathL stores
-        if ((e = begin()) != hipSuccess) return e;
+        e = stage([&] {
+            if (split) {  // the shading list first: it feeds queue 4
+                (void)kernel(p->ws.microfacet ? k_pt_resume3_shade<true> : k_pt_resume3_shade<false>, pg, stream);
+                return forked ? hipSuccess : kernel(k_pt_resume3_lean, pg, stream);
+            }
+            return kernel(p->ws.microfacet ? k_pt_resume<3, true, false>
+                          : p->ws.glossy   ? k_pt_resume<3, false, true>
+                                           : k_pt_resume<3, false, false>, pg, stream);
+        });
+        if (e == hipSuccess) e = stage([&] { return rtk_launch_trace_queue(p, 4, stream); });
+        if (e == hipSuccess) e = stage([&] { return kernel(k_pt_resume<4, false, false>, pg, stream); });  // step 4 shades nothing
+        if (e == hipSuccess && forked) e = hipStreamWaitEvent(stream, fork->done, 0);  // its pathL stores
+        if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_pt_resolve, dim3(p->ws.persistBlocks), dim3(256), 0, stream, *p);
-    if ((e = end()) != hipSuccess) return e;
+    if ((e = stage([&] { return kernel(k_pt_resolve, pg, stream); })) != hipSuccess) return e;
     return hipGetLastError();
 }
 }  // namespace

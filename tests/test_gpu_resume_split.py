@@ -28,10 +28,9 @@ def cameras(rtx, oracle, w, h, kind):
     return oracle.default_camera(w, h), None
 
 
-def trace(rtx, tmp_path, w, h, spp, split, rcam=None, extra=""):
-    """One detail launch of frame FRAME as four lean kernels (chain off): G-buffers, RAYS, counters."""
-    cfg = rtx.write_config(str(tmp_path / ("s%d.toml" % split)), w, h, spp=spp, extra=extra,
-                           tuning={"chain": "off", "resumeSplit": split})
+def launch(rtx, tmp_path, name, w, h, spp, tuning, rcam=None, extra=""):
+    """One detail launch of frame FRAME: G-buffers (with RAYS), counters, ray count, PT_STATS [P, 4]."""
+    cfg = rtx.write_config(str(tmp_path / (name + ".toml")), w, h, spp=spp, extra=extra, tuning=tuning)
     rt = rtx.RayTracer(w, h, cfg).init()
     if rcam is not None:
         rt.camera = rcam
@@ -40,9 +39,15 @@ def trace(rtx, tmp_path, w, h, spp, split, rcam=None, extra=""):
     rt.sync()
     g = gpu_gbuffers(rt, w, h)
     q = rt.download("PT_QUEUE", np.uint32).copy()
+    st = rt.download("PT_STATS", np.uint32).reshape(-1, 4)[:w * h].copy()
     rays = rt.ray_count()
     rt.cleanup()
-    return g, q, rays
+    return g, q, rays, st
+
+
+def trace(rtx, tmp_path, w, h, spp, split, rcam=None, extra=""):
+    """... as four lean kernels (chain off): G-buffers, RAYS, counters."""
+    return launch(rtx, tmp_path, "s%d" % split, w, h, spp, {"chain": "off", "resumeSplit": split}, rcam, extra)[:3]
 
 
 @pytest.mark.parametrize("cam_kind", ["terrain", "default", "sky"])
@@ -85,6 +90,35 @@ def test_shading_list_counts_the_d1_events(rtx, oracle, tmp_path):
         assert q[21] > 0
         assert q[23] == q[21], (q[23], q[21])
         assert q[23] < q[0]  # shadow rays and misses are not listed
+
+
+@pytest.mark.parametrize("w,h", [(192, 108), (100, 60)])  # 100x60: no multiple of the 64-lane batches
+def test_chain_and_four_kernels_agree_on_detail_counts(rtx, oracle, tmp_path, w, h):
+    """What a detail launch counts behind resume_entry — RAYS, PT_STATS, the ray total and the work
+    counters — comes from one routine (finish_entry) in the fused chain, the unsplit resume<3> and the
+    split one, so the three agree exactly.  The chain sums kCntDiffRes3 (counter 21) per wave like the
+    kernels do.  Node visits and triangle tests (PT_STATS columns 1 and 2) are compared between the
+    two four-kernel variants only: the chain's tracer loads its records differently and may count
+    them differently."""
+    _, rcam = terrain_camera(rtx, oracle, w, h)
+    variants = [("chain", {"chain": "always"}), ("unsplit", {"chain": "off", "resumeSplit": 0}),
+                ("split", {"chain": "off", "resumeSplit": 1})]
+    (g0, q0, rays0, st0), unsplit, split = (launch(rtx, tmp_path, name, w, h, 4, tuning, rcam)
+                                            for name, tuning in variants)
+    assert q0[0] > 256  # more than one workgroup's entries
+    assert q0[21] > 0 and st0[:, 3].sum() > 0
+    for g, q, rays, st in (unsplit, split):
+        assert_gbuffers_equal(g, g0)  # RAYS among them
+        assert rays == rays0
+        for col in (0, 3):  # rays, diffuse events per pixel
+            assert np.array_equal(st[:, col], st0[:, col]), col
+        for k in (0, 1, 4, 11, 20, 21):
+            assert q[k] == q0[k], k
+    for q in (q0, unsplit[1], split[1]):
+        assert q[10] == 0  # kCntError
+    assert np.array_equal(unsplit[3][:, 1:3], split[3][:, 1:3])
+    assert np.array_equal(st0[:, 0], g0["rays"])  # the two per-pixel ray counts are one count
+    assert rays0 == int(g0["rays"].sum())
 
 
 def test_emissive_override_finishes_without_shading(rtx, oracle, tmp_path, default_scene, sky_tex):
