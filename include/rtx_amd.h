@@ -75,7 +75,8 @@ int rt_init(rt_context* ctx);
  * next frame's camera-ray and shade kernels ahead, beside this frame's bounces and denoise, into
  * the other G-buffer set ([tuning] syncSpec): the draw still returns with its frame complete, and
  * those kernels may still run on the context's side stream.  The next draw uses their results only
- * when its launch parameters (camera, sky, size, frame number, materials, buffers) equal theirs;
+ * when its launch parameters (camera, sky, size, frame number, materials, buffers) and the geometry
+ * epoch (rt_update_vertices) equal theirs;
  * any call that waits for the streams (rt_sync, the reads, the setters) discards them first. */
 int rt_draw(rt_context* ctx, uint8_t* rgba8_out, float* hdr_out);
 
@@ -271,6 +272,51 @@ size_t rt_buffer_bytes(const rt_context* ctx, int name); /* 0 for names not avai
  * enqueued on the context stream (asynchronous). */
 int rt_build_bvh(rt_context* ctx);
 
+/* Animated geometry (no reference counterpart: the reference uploads its mesh once, init.cu:78-130,
+ * and rebuilds the same LBVH every frame): new positions for vertices [first, first + count).
+ *
+ * Effect: afterwards the vertices, the smooth normals (recomputed for the whole mesh) and every
+ * later LBVH build equal those of a context whose rt_init had been given the new positions; for the
+ * normals that is the reference's frame-1 sequence, GenerateSmoothNormals run twice into an
+ * un-cleared buffer, angle-weighted, accumulated in triangle order (kernel.cu:228-257, 313-327), bit
+ * for bit.  rt_download(RT_ARR_VERTICES / RT_ARR_NORMALS) return the updated arrays.
+ *
+ * Scope: the topology (indices, triangle and batch counts) is fixed.  The update takes effect for
+ * every rt_build_bvh, explicit or inside a draw, enqueued after the call; frames already enqueued,
+ * pipelined ones included, keep the geometry they were built from.  Nothing rebuilds by itself:
+ * rt_trace_rays and rt_trace_primary still use the BVH of the last rt_build_bvh.
+ *
+ * Ordering inside the renderer: the update runs after the last build enqueued on any of the
+ * renderer's streams, the next build on whichever stream waits for it, and work enqueued on the
+ * context stream (rt_set_stream) after the call follows the read of the caller's buffer, so a
+ * framework tensor allocated on that stream can be reused at once.
+ *
+ * rt_update_vertices: host positions (count xyz triples), copied synchronously into a staging
+ * buffer of the renderer; the caller's array is free on return.
+ * rt_update_vertices_device: caller-owned device memory (4-byte aligned); asynchronous, the host is
+ * not synchronised.  ready_event NULL: the source is read after everything enqueued on the context
+ * stream so far — always safe for data produced on that stream, but on a pipelined context it puts
+ * the next frame's build behind the current frame's trace.  ready_event a hipEvent_t: the update
+ * waits for that event only; a host that animates on a stream of its own records one there and keeps
+ * the frames overlapped.  The source must stay unchanged until the update has read it (work
+ * enqueued on the context stream after the call is behind that point).
+ *
+ * Each update advances the geometry epoch (0 after rt_init).  What synchronous draws prepare ahead —
+ * the next frame's LBVH, its camera rays and shading — carries its epoch and is built or traced
+ * again by a draw that finds another one, so no draw shows geometry older than the last update.
+ *
+ * Temporal passes: history reprojection stays camera-only, as in the reference
+ * (temporalDenoising.cuh); there are no motion vectors for geometry, so moving geometry ghosts as it
+ * would there.  Multi-GPU: every rank calls the update with the same data.
+ *
+ * RT_ERR_ARG: NULL context or pointer, count == 0, first + count > vertexCount (rt_get_info), a
+ * misaligned device pointer; RT_ERR_STATE before rt_init.  Like the other setters they never
+ * return RT_ERR_DEVICE. */
+int rt_update_vertices(rt_context* ctx, const float* xyz, uint32_t first, uint32_t count);
+int rt_update_vertices_device(rt_context* ctx, const float* xyz_device, uint32_t first, uint32_t count,
+                              void* ready_event);
+int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch); /* 0 after rt_init, +1 per update */
+
 /* BASELINE config 2: GenerateRay + RaySceneIntersect for every render pixel with the
  * blue-noise sample of frame_num (pathtrace.cuh:116-130), enqueued asynchronously.
  * with_detail != 0 also stores normals / shading normals / traversal counters. */
@@ -375,7 +421,8 @@ int rt_sync(rt_context* ctx);
 
 /* HIP-event timing on the context stream: runs `iters` back-to-back launches of a stage
  * (0 = BVH build, 1 = primary rays, 2 = path trace, 3 = full frame: BVH + path trace + denoise
- * + post, 4 = denoise + post) and returns the total
+ * + post, 4 = denoise + post, 5 = a whole-mesh vertex update with its smooth normals, fed the
+ * current positions from a copy: arrays and epoch stay as they are) and returns the total
  * milliseconds between the first launch and the end of the last. */
 int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms);
 

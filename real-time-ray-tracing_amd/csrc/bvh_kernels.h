@@ -108,6 +108,21 @@ struct TracePrimaryParams {
     uint32_t* statsOut;         // [W*H][4] optional: visits, tests, dropped, iterations
 };
 
+// One vertex update (geometry.hip): new positions for vertices [first, first + count) and the smooth
+// normals of the whole mesh, the values k_smooth_normals gives for the updated positions.
+struct GeomUpdateParams {
+    const float* src;            // [count][3] positions of vertices [first, first + count) (device memory)
+    uint32_t first, count;
+    float* vertices;             // [nverts][3], the range is rewritten
+    float* normals;              // [nverts][3], rewritten whole
+    const uint32_t* indices;     // [triCountPadded][3]
+    const uint32_t* cornerSlot;  // [triCountPadded * 3] corner -> its place in the vertex -> corner CSR
+    const uint32_t* adjOffsets;  // [nverts + 1] the CSR's offsets
+    float* contrib;              // [triCountPadded * 3][3] scratch: the corners' contributions in CSR order
+    uint32_t nverts, triCountPadded;
+};
+
+extern "C" hipError_t rtk_launch_geometry_update(const GeomUpdateParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_build_bvh(const BvhBuildParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_trace_primary(const TracePrimaryParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_smooth_normals(const float* vertices, const uint32_t* adjOffsets,

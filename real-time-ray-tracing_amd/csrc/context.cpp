@@ -477,12 +477,16 @@ int rt_init(rt_context* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->dBlueNoise, bn.data(), bn.size(), hipMemcpyHostToDevice));
 
     // ---- frame-1 smooth normals (kernel.cu:313-327): vertex -> corner CSR in triangle order
+    std::vector<uint32_t> slots((size_t)NP * 3);  // the CSR's inverse, corner -> slot (vertex updates)
     {
         std::vector<uint32_t> off(ctx->nv + 1, 0), corners((size_t)NP * 3);
         for (size_t c = 0; c < (size_t)NP * 3; ++c) off[ctx->mesh.indices[c] + 1]++;
         for (uint32_t v = 0; v < ctx->nv; ++v) off[v + 1] += off[v];
         std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-        for (size_t c = 0; c < (size_t)NP * 3; ++c) corners[fill[ctx->mesh.indices[c]]++] = (uint32_t)c;
+        for (size_t c = 0; c < (size_t)NP * 3; ++c) {
+            slots[c] = fill[ctx->mesh.indices[c]]++;
+            corners[slots[c]] = (uint32_t)c;
+        }
         ALLOC(ctx->dAdjOff, off.size() * 4);
         ALLOC(ctx->dAdjCorner, corners.size() * 4);
         HIP_TRY(ctx, hipMemcpy(ctx->dAdjOff, off.data(), off.size() * 4, hipMemcpyHostToDevice));
@@ -492,6 +496,13 @@ int rt_init(rt_context* ctx) {
     }
 #undef ALLOC
     if ((rc = rt_frame_init(ctx)) != RT_OK) return rc;
+    // vertex updates (rt_update_vertices*, geometry.hip): their scratch and events exist from here on,
+    // so that an update only enqueues work
+    if ((rc = dalloc(ctx, &ctx->dCornerSlot, slots.size() * 4)) != RT_OK) return rc;
+    if ((rc = dalloc(ctx, &ctx->dContrib, slots.size() * 12)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->dCornerSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomSrc, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomDone, hipEventDisableTiming));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->inited = true;
     // CameraSetup (init.cu:433-435): a missing or short file leaves the default camera, and the
@@ -505,7 +516,7 @@ void rt_destroy(rt_context* ctx) {
     if (!ctx) return;
     if (ctx->inited) (void)sync_streams(ctx, false);  // also when the context stream is the null stream
     for (hipEvent_t e : {ctx->overlapEv, ctx->cameraGate, ctx->specGate, ctx->specDone, ctx->buildDone[0], ctx->buildDone[1],
-                         ctx->bvhFree[0], ctx->bvhFree[1]})
+                         ctx->bvhFree[0], ctx->bvhFree[1], ctx->geomSrc, ctx->geomDone})
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kGbSets; ++k)
         for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k],
@@ -619,7 +630,8 @@ int rt_build_bvh(rt_context* ctx) {
     if (int rc = check_device_status(ctx)) return rc;  // a previous build's failure, once it is known
     hipStream_t stream = ctx->stream;
     // camera rays a synchronous draw traced ahead read this set (frame.cpp launch_spec_camera): the
-    // rebuild writes the same values, but after them
+    // rebuild overwrites it only after them.  It writes the same values while the geometry epoch is
+    // theirs; after a vertex update it does not, and the next path trace drops them (spec_matches)
     if (ctx->fr.spec.valid) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->specDone, 0));
     ctx->bvhPrebuilt = false;  // an explicit build supersedes a synchronous draw's prebuild
     if (!ctx->postStream) ctx->buildOnSide[ctx->bvhSet] = false;
@@ -629,6 +641,8 @@ int rt_build_bvh(rt_context* ctx) {
         bvh_select(ctx, k);
         stream = ctx->sideStream;
     }
+    // the build gathers the vertices and normals of the last update, whichever stream that ran on
+    if (ctx->geomDoneValid && stream != ctx->geomStream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->geomDone, 0));
     BvhBuildParams p;
     p.vertices = ctx->dVerts;
     p.normals = ctx->dNormals;
@@ -660,7 +674,93 @@ int rt_build_bvh(rt_context* ctx) {
     if (ctx->postStream) {
         HIP_TRY(ctx, hipEventRecord(ctx->buildDone[ctx->bvhSet], stream));
         ctx->buildOnSide[ctx->bvhSet] = true;
+        ctx->sideBuilt[ctx->bvhSet] = true;
     }
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- animated geometry
+//
+// One update on stream U: the side stream on a pipelined context (where every build runs, so the
+// update is behind the last one and ahead of the next without an event, and beside the current
+// frame's trace chain), else the context stream.  `srcReady`: the source needs no ordering (the
+// renderer's staging copy); otherwise U waits for `ready`, or without one for the context stream.
+static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t first, uint32_t count, hipEvent_t ready,
+                                 bool srcReady, bool bump) {
+    hipStream_t u = ctx->postStream ? ctx->sideStream : ctx->stream;
+    if (!srcReady) {
+        if (ready) {
+            HIP_TRY(ctx, hipStreamWaitEvent(u, ready, 0));
+        } else if (u != ctx->stream) {
+            HIP_TRY(ctx, hipEventRecord(ctx->geomSrc, ctx->stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->geomSrc, 0));
+        }
+    }
+    // the builds that still gather the old positions: a synchronous draw's prebuild on the side stream
+    // (the context stream's own builds are ahead of the update there), an earlier update elsewhere
+    if (u != ctx->sideStream)
+        for (int k = 0; k < 2; ++k)
+            if (ctx->sideBuilt[k]) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->buildDone[k], 0));
+    if (ctx->geomDoneValid && ctx->geomStream != u) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->geomDone, 0));
+    GeomUpdateParams p;
+    p.src = src;
+    p.first = first;
+    p.count = count;
+    p.vertices = ctx->dVerts;
+    p.normals = ctx->dNormals;
+    p.indices = ctx->dIdx;
+    p.cornerSlot = ctx->dCornerSlot;
+    p.adjOffsets = ctx->dAdjOff;
+    p.contrib = ctx->dContrib;
+    p.nverts = ctx->nv;
+    p.triCountPadded = ctx->mesh.triCountPadded;
+    HIP_TRY(ctx, rtk_launch_geometry_update(&p, u));
+    HIP_TRY(ctx, hipEventRecord(ctx->geomDone, u));
+    ctx->geomStream = u;
+    ctx->geomDoneValid = true;
+    // what the caller enqueues on the context stream from here on follows the read of its buffer
+    if (u != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->geomDone, 0));
+    if (bump) ++ctx->geomEpoch;
+    return RT_OK;
+}
+
+static int check_vertex_range(rt_context* ctx, const void* xyz, uint32_t first, uint32_t count, const char* who) {
+    if (!ctx || !xyz) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = std::string(who) + " before rt_init"; return RT_ERR_STATE; }
+    if (count == 0 || (uint64_t)first + (uint64_t)count > (uint64_t)ctx->nv) {
+        ctx->err = std::string(who) + ": [first, first + count) must be a non-empty range of the mesh's vertices";
+        return RT_ERR_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_update_vertices_device(rt_context* ctx, const float* xyz_device, uint32_t first, uint32_t count,
+                              void* ready_event) {
+    if (int rc = check_vertex_range(ctx, xyz_device, first, count, "rt_update_vertices_device")) return rc;
+    if (((uintptr_t)xyz_device & 3u) != 0) { ctx->err = "rt_update_vertices_device: positions must be 4-byte aligned"; return RT_ERR_ARG; }
+    return enqueue_vertex_update(ctx, xyz_device, first, count, (hipEvent_t)ready_event, false, true);
+}
+
+// the staging buffer, once no earlier update still reads it
+static int vertex_stage(rt_context* ctx) {
+    if (!ctx->dVertStage) {
+        if (int rc = dalloc(ctx, &ctx->dVertStage, (size_t)ctx->nv * 12)) return rc;
+    }
+    if (ctx->geomDoneValid) HIP_TRY(ctx, hipEventSynchronize(ctx->geomDone));
+    return RT_OK;
+}
+
+int rt_update_vertices(rt_context* ctx, const float* xyz, uint32_t first, uint32_t count) {
+    if (int rc = check_vertex_range(ctx, xyz, first, count, "rt_update_vertices")) return rc;
+    if (int rc = vertex_stage(ctx)) return rc;
+    float* stage = ctx->dVertStage + 3 * (size_t)first;
+    HIP_TRY(ctx, hipMemcpy(stage, xyz, (size_t)count * 12, hipMemcpyHostToDevice));
+    return enqueue_vertex_update(ctx, stage, first, count, nullptr, true, true);
+}
+
+int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch) {
+    if (!ctx || !epoch) return RT_ERR_ARG;
+    *epoch = ctx->geomEpoch;
     return RT_OK;
 }
 
@@ -717,10 +817,18 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
         const int rc2 = rt_set_post_stream(ctx, post);
         return rc != RT_OK ? rc : rc2;
     }
+    if (stage == 5) {  // the current positions again, from a copy: the arrays and the epoch stay as they are
+        int rc = sync_streams(ctx, false);
+        if (rc == RT_OK) rc = vertex_stage(ctx);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(ctx, hipMemcpy(ctx->dVertStage, ctx->dVerts, (size_t)ctx->nv * 12, hipMemcpyDeviceToDevice));
+        HIP_TRY(ctx, hipDeviceSynchronize());
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (int i = 0; i < iters; ++i) {
         int rc = RT_OK;
         if (stage == 0) rc = rt_build_bvh(ctx);
+        else if (stage == 5) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false);
         else if (stage == 1) rc = rt_trace_primary(ctx, 1 + i, 0);
         else if (stage == 2) rc = rt_path_trace(ctx, 1 + i, 0);
         else if (stage == 3) {

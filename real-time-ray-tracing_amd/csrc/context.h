@@ -114,6 +114,7 @@ struct FrameResources {
         bool valid = false;
         bool shade = false;  // the shade kernel went ahead too
         int block = 0;
+        uint64_t epoch = 0;  // the geometry epoch of the LBVH they were traced on
         PathTraceParams p{};
     } spec;
     bool specReady = false;          // set 1's buffers and the events exist (ensure_sync_spec)
@@ -277,6 +278,19 @@ struct rt_context {
     BvhBufs bvh[2];
     int bvhSet = 0;
     bool bvhPrebuilt = false;  // synchronous draws: the next frame's LBVH is being built into set bvhSet ^ 1
+    uint64_t prebuiltEpoch = 0;  // ... from the geometry of this epoch; a draw at another epoch rebuilds
+    // animated geometry (rt_update_vertices*).  The build's gather and the normals
+    // kernels are the only device readers of dVerts / dNormals, so there is one vertex set: an update
+    // is enqueued behind the last build of every stream and the next build waits for geomDone.
+    uint64_t geomEpoch = 0;             // 0 after rt_init, +1 per update
+    hipEvent_t geomSrc = nullptr;       // the context stream's work up to an update without a ready event
+    hipEvent_t geomDone = nullptr;      // the last update's end
+    hipStream_t geomStream = nullptr;   // ... and the stream it ran on
+    bool geomDoneValid = false;         // geomDone is recorded and a stream may still have to wait for it
+    bool sideBuilt[2] = {false, false}; // buildDone[k] has been recorded (a build of set k on the side stream)
+    uint32_t* dCornerSlot = nullptr;    // corner -> slot in the vertex -> corner CSR (dAdjCorner's inverse)
+    float* dContrib = nullptr;          // the corners' normal contributions in CSR order (geometry.hip)
+    float* dVertStage = nullptr;        // rt_update_vertices' host positions / rt_time_stage(5)'s copy
     // frame pipelining: rt_denoise_post(f) is enqueued on the post stream only once the next
     // path trace has enqueued kernel `overlapAfter` (so it fills the trace stages' idle tails), or
     // at the next host read / denoise call, whichever comes first

@@ -328,6 +328,7 @@ int sync_streams(rt_context* ctx, bool report) {
     // joined into the context stream before each resolve; on its own only after a failed launch
     if (ctx->leanStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->leanStream));
     if (ctx->postStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->postStream));
+    ctx->geomDoneValid = false;  // a vertex update ran on one of these streams: no build waits for it now
     poll_q3(ctx);
     // camera rays a synchronous draw traced ahead are kept only up to the next draw: any call that
     // waits for the streams (a read, a setter, a mode change) drops them
@@ -746,13 +747,14 @@ bool spec_on(const rt_context* ctx) {
 
 // whether the camera and shade kernels launched with `a` wrote what ones launched with `b` would:
 // the same parameters but for those they do not read (or that only select the later kernels)
-bool spec_matches(const PathTraceParams& a, const PathTraceParams& b) {
+bool spec_matches(const PathTraceParams& a, uint64_t epochA, const PathTraceParams& b, uint64_t epochB) {
+    // they read the LBVH set of the frame that launched them, the next frame reads the other: both
+    // hold the same build (tests/test_gpu_bvh.py) exactly when no vertex update came between them
+    if (epochA != epochB) return false;
     PathTraceParams x = a, y = b;
     for (PathTraceParams* q : {&x, &y}) {
         q->rayCounter = nullptr;  // the launches ahead count into specRayCounter
-        // they read the LBVH set of the frame that launched them, the next frame reads the other:
-        // the geometry is fixed after rt_init, so both hold the same build (tests/test_gpu_bvh.py)
-        q->nodes = q->tlasNodes = nullptr;
+        q->nodes = q->tlasNodes = nullptr;  // the two LBVH sets of one geometry epoch (above)
         q->triPos = nullptr;
         q->triNrm = nullptr;
         q->ws.traceBlocks = 0;
@@ -861,7 +863,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     if (fr.spec.valid) {
         fr.spec.valid = false;
         HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->specDone, 0));
-        reuse = !side && spec_matches(p, fr.spec.p);
+        reuse = !side && spec_matches(p, ctx->geomEpoch, fr.spec.p, fr.spec.epoch);
         reuseShade = reuse && fr.spec.shade;
         if (!reuse) p.ws.countersZeroed = 0;  // their counts are in the block: the launcher clears it
         fr.specCounts = reuse ? 1 : 2;  // folded into the frame's (or cleared) ahead of the next ones
@@ -1121,9 +1123,10 @@ int copy_rgba_out(rt_context* ctx, void* dst) {
 namespace {
 // Synchronous draws: the next frame's LBVH rebuild (BuildBvhLevel1/2, one per frame as in the
 // reference) goes into the other set on the side stream, where it runs beside this frame's
-// denoise instead of ahead of the next frame's path trace.  The geometry is fixed after rt_init,
-// so the build depends on nothing this frame computes; the other set was last read by the
-// previous frame, which has finished.
+// denoise instead of ahead of the next frame's path trace.  The build depends on nothing this
+// frame computes, only on the geometry: it carries the epoch it gathered (prebuiltEpoch), and a
+// draw that finds another one (a vertex update since) builds again.  The other set was last read
+// by the previous frame, which has finished.
 int prebuild_next_bvh(rt_context* ctx) {
     int rc;
     if ((rc = ensure_bvh_pair(ctx)) != RT_OK) return rc;
@@ -1139,9 +1142,11 @@ int prebuild_next_bvh(rt_context* ctx) {
             rc = RT_ERR_HIP;
         }
         ctx->buildOnSide[cur ^ 1] = true;
+        ctx->sideBuilt[cur ^ 1] = true;
     }
     bvh_select(ctx, cur);
     ctx->bvhPrebuilt = rc == RT_OK;
+    ctx->prebuiltEpoch = ctx->geomEpoch;
     return rc;
 }
 
@@ -1175,9 +1180,9 @@ int ensure_sync_spec(rt_context* ctx) {
 // and frame number as they are now.
 // They then run beside this frame's bounces and denoise instead of at the head of the next draw.
 // The next rt_path_trace uses them only when its own launch parameters equal these (spec_matches:
-// a host that moves the camera, changes the sky, the size or the frame number between the draws
-// gets them traced again), and any call that waits for the streams drops them, so no draw's output
-// depends on this.
+// a host that moves the camera, changes the sky, the size or the frame number, or updates vertices
+// (another geometry epoch) between the draws gets them traced again), and any call that waits for
+// the streams drops them, so no draw's output depends on this.
 int launch_spec_camera(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
     if (!ctx->tune.syncSpec || ctx->postStream || ctx->stripCount != 1 || fr.gbBound) return RT_OK;
@@ -1213,6 +1218,7 @@ int launch_spec_camera(rt_context* ctx) {
     fr.spec.valid = true;
     fr.spec.shade = shade;
     fr.spec.block = b;
+    fr.spec.epoch = ctx->geomEpoch;  // of this frame's LBVH, built or checked by enqueue_frame just before
     fr.spec.p = p;
     return RT_OK;
 }
@@ -1228,7 +1234,8 @@ int enqueue_frame(rt_context* ctx, uint32_t* target, uint32_t pitch, bool hdr) {
     if (ctx->useDynamicResolution && frame > 1 && ctx->fullFrame) update_dynamic_resolution(ctx, dt);
     rt_input_control_update(ctx, dt);  // UpdateFrame's InputControlUpdate (kernel.cu:117)
     ctx->fr.drawDt = dt;
-    if (ctx->bvhPrebuilt && !ctx->postStream) {  // built beside the previous synchronous frame
+    // built beside the previous synchronous frame, from the geometry this frame draws
+    if (ctx->bvhPrebuilt && !ctx->postStream && ctx->prebuiltEpoch == ctx->geomEpoch) {
         ctx->bvhPrebuilt = false;
         bvh_select(ctx, ctx->bvhSet ^ 1);  // the path trace waits for its build (wait_bvh)
     } else if ((rc = rt_build_bvh(ctx)) != RT_OK) {

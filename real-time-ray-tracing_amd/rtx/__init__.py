@@ -149,6 +149,9 @@ SIGNATURES = {
     "rt_scan_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rt_frame_marks_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "rt_frame_marks_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
+    "rt_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_get_geometry_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 IMAGE_PPM_RGBA8, IMAGE_PFM_HDR = 0, 1
 DRAW_ASYNC = 1  # rt_draw_device flag
@@ -330,6 +333,34 @@ class RayTracer:
     # ---- hot-path stages
     def build_bvh(self):
         self._check(self.lib.rt_build_bvh(self.h), "rt_build_bvh")
+
+    # ---- animated geometry (rt_update_vertices*, include/rtx_amd.h)
+    def update_vertices(self, xyz: np.ndarray, first: int = 0):
+        """New positions for vertices [first, first + len(xyz)) from a C-contiguous (n, 3) float32
+        array; the smooth normals of the whole mesh follow, and every later build_bvh / draw."""
+        if not isinstance(xyz, np.ndarray) or xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("update_vertices: xyz must be an (n, 3) float32 array")
+        if not xyz.flags["C_CONTIGUOUS"]:
+            raise ValueError("update_vertices: xyz must be C-contiguous")
+        if not 0 <= int(first) <= 0xFFFFFFFF or len(xyz) > 0xFFFFFFFF:
+            raise ValueError("update_vertices: first and the vertex count must fit 32 bits")
+        self._check(self.lib.rt_update_vertices(self.h, xyz.ctypes.data, int(first), len(xyz)), "rt_update_vertices")
+
+    def update_vertices_device(self, ptr: int, count: int, first: int = 0, ready_event: int | None = None):
+        """The same from device memory (count xyz float32 triples at ptr), asynchronous.  ready_event:
+        a hipEvent_t handle (e.g. torch.cuda.Event.cuda_event) the read waits for; None: the read
+        follows everything enqueued on the context stream so far."""
+        if not 0 <= int(first) <= 0xFFFFFFFF or not 0 <= int(count) <= 0xFFFFFFFF:
+            raise ValueError("update_vertices_device: first and count must fit 32 bits")
+        self._check(self.lib.rt_update_vertices_device(self.h, ptr, int(first), int(count), ready_event),
+                    "rt_update_vertices_device")
+
+    @property
+    def geometry_epoch(self) -> int:
+        """0 after init, +1 per vertex update."""
+        v = C.c_uint64()
+        self._check(self.lib.rt_get_geometry_epoch(self.h, C.byref(v)), "rt_get_geometry_epoch")
+        return v.value
 
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")

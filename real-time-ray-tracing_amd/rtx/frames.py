@@ -59,11 +59,23 @@ class FramePipeline:
         self.need = ([gbuffer_rows(info.renderHeight, world, r) for r in range(world)]
                      if self.denoise is not None else None)
 
-    def frame(self, f: int, hdr: bool = False):
-        """LBVH rebuild, path trace, (gather,) denoise + post of frame f, enqueued asynchronously."""
+    def frame(self, f: int, hdr: bool = False, vertices=None, vertices_ready=None):
+        """LBVH rebuild, path trace, (gather,) denoise + post of frame f, enqueued asynchronously.
+
+        vertices: a device float32 tensor (n, 3), the positions of vertices [0, n) from this frame
+        on (rt_update_vertices_device), applied ahead of the rebuild.  vertices_ready: a recorded
+        torch.cuda.Event the read of the tensor waits for, when the host animates on a stream of
+        its own; None: the read follows everything enqueued on the renderer's stream so far.  The
+        tensor must stay unchanged until then; every rank passes the same data."""
         import torch
 
         rt = self.rt
+        if vertices is not None:
+            if (vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3
+                    or not vertices.is_contiguous() or not vertices.is_cuda):
+                raise ValueError("vertices must be a contiguous (n, 3) float32 device tensor")
+            ev = None if vertices_ready is None else vertices_ready.cuda_event
+            rt.update_vertices_device(vertices.data_ptr(), vertices.shape[0], 0, ev)
         rt.build_bvh()
         rt.path_trace(f)
         if self.gather is not None:
