@@ -40,7 +40,9 @@ typedef struct rt_context rt_context;
 /* RayTracer::RayTracer(screenWidth, screenHeight), kernel.cuh:435-441, plus LoadConfig
  * (configLoader.cpp:5-27).  config_toml may be NULL (defaults) or a path to a TOML file with
  * the reference's [resolution] / [file] / [optimziation] tables; extensions: [scene]
- * chunkDim (VoxelsGenerator::kChunkDim, terrain.h:42), [render] spp, [render] device.
+ * chunkDim (VoxelsGenerator::kChunkDim, terrain.h:42), [render] spp, [render] device, [render]
+ * geometryMotion (true | false, default false: rt_set_geometry_motion's initial state; any other
+ * value is refused with RT_ERR_IO).
  * [tuning] (scheduling A/B aids; the defaults are the measured best): arena (bool),
  * streams ("cumask" | "prio"), tracePerCu / trace4PerCu (0: automatic), trace3ShortPerCu (a short queue
  * 3's workgroups per CU on one GPU; 0: all of them), chain ("serial" | "off" |
@@ -305,9 +307,11 @@ int rt_build_bvh(rt_context* ctx);
  * the next frame's LBVH, its camera rays and shading — carries its epoch and is built or traced
  * again by a draw that finds another one, so no draw shows geometry older than the last update.
  *
- * Temporal passes: history reprojection stays camera-only, as in the reference
- * (temporalDenoising.cuh); there are no motion vectors for geometry, so moving geometry ghosts as it
- * would there.  Multi-GPU: every rank calls the update with the same data.
+ * Temporal passes: by default history reprojection is camera-only, as in the reference
+ * (temporalDenoising.cuh), and moving geometry ghosts as it would there.  With geometry motion
+ * vectors on (rt_set_geometry_motion below) RT_BUF_MOTION follows the vertices, and the temporal
+ * filters fetch their history where the surface was.  Multi-GPU: every rank calls the update with
+ * the same data.
  *
  * RT_ERR_ARG: NULL context or pointer, count == 0, first + count > vertexCount (rt_get_info), a
  * misaligned device pointer; RT_ERR_STATE before rt_init.  Like the other setters they never
@@ -316,6 +320,34 @@ int rt_update_vertices(rt_context* ctx, const float* xyz, uint32_t first, uint32
 int rt_update_vertices_device(rt_context* ctx, const float* xyz_device, uint32_t first, uint32_t count,
                               void* ready_event);
 int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch); /* 0 after rt_init, +1 per update */
+
+/* Geometry motion vectors (no reference counterpart): off by default, and off nothing changes.  On,
+ * the RT_BUF_MOTION G-buffer of a frame accounts for the vertices' displacement between the LBVH
+ * build the frame is traced on and the build before it: a pixel whose sample 0 hit a triangle at
+ * barycentrics (u, v) was at  pos - (d3 (1 - u - v) + d1 u + d2 v)  in the previous frame, d1..d3
+ * the displacement of the triangle's corners between the two builds, and its motion vector is the
+ * history camera's projection of that point less the sample's screen position (the camera-only
+ * formula with the previous position in place of pos; NaN handling, bias and half packing as
+ * before).  A pixel whose sample 0 missed keeps (0.5, 0.5).  A triangle whose corners did not move
+ * gets the camera-only value bit for bit.
+ *
+ * Which builds record a displacement: one at another geometry epoch than the build before it, when
+ * the feature was on at the first update between the two.  The first build of a context, a build at
+ * the previous build's epoch (a synchronous draw's prebuild included) and the builds of a context
+ * that never updates record none, and the path trace on them launches the kernels it launches with
+ * the feature off.  Several updates between two builds are one displacement, from the previous
+ * build's positions to the last update's.  Only the first rt_path_trace enqueued on a build applies
+ * it: a host that builds once and traces several frames sees geometry that did not move between
+ * them.  What a synchronous draw traces ahead for the next frame never carries one; when a draw
+ * discards that and traces again, the repeat is the frame's one path trace.
+ *
+ * rt_set_geometry_motion waits for the streams like the other setters, allocates its buffers on the
+ * first enable (one position array, one displacement record per triangle and LBVH set) and takes
+ * effect from the next build.  [render] geometryMotion = true | false sets the initial state.
+ * RT_ERR_ARG: NULL argument; RT_ERR_STATE: rt_set_geometry_motion before rt_init; RT_ERR_HIP: the
+ * buffers cannot be allocated.  Never RT_ERR_DEVICE. */
+int rt_set_geometry_motion(rt_context* ctx, int on);
+int rt_get_geometry_motion(const rt_context* ctx, int* on);
 
 /* BASELINE config 2: GenerateRay + RaySceneIntersect for every render pixel with the
  * blue-noise sample of frame_num (pathtrace.cuh:116-130), enqueued asynchronously.

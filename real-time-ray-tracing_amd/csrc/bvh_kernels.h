@@ -120,9 +120,23 @@ struct GeomUpdateParams {
     const uint32_t* adjOffsets;  // [nverts + 1] the CSR's offsets
     float* contrib;              // [triCountPadded * 3][3] scratch: the corners' contributions in CSR order
     uint32_t nverts, triCountPadded;
+    float* prevVerts;            // optional [nverts][3]: the whole mesh's positions before this update
+                                 // (geometry motion vectors: the first update after a build)
+};
+
+// The displacement records of one LBVH set (geometry motion vectors, geometry.hip): per triangle
+// record, in the records' order (the mesh's: bvh_build.hip gathers triangle g into record g), the
+// three corners' position at this build minus their position at the previous build.
+struct GeomDispParams {
+    const float* vertices;       // [nverts][3] the positions the build gathered
+    const float* prevVerts;      // [nverts][3] the positions the previous build gathered
+    const uint32_t* indices;     // [triCountPadded][3]
+    float4* triDisp;             // [triCountPadded][3] d1, d2, d3 in the order of the record's v1, v2, v3
+    uint32_t triCountPadded;
 };
 
 extern "C" hipError_t rtk_launch_geometry_update(const GeomUpdateParams* p, hipStream_t stream);
+extern "C" hipError_t rtk_launch_geometry_displacement(const GeomDispParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_build_bvh(const BvhBuildParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_trace_primary(const TracePrimaryParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_smooth_normals(const float* vertices, const uint32_t* adjOffsets,

@@ -322,6 +322,14 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
     ctx->stripCount = rttoml::find_or_int(doc, "render", "stripCount", 1);
     ctx->stripIndex = rttoml::find_or_int(doc, "render", "stripIndex", 0);
     ctx->materialOverride = rttoml::find_or_int(doc, "render", "materialOverride", -1);
+    if (const rttoml::Value* v = rttoml::find(doc, "render", "geometryMotion")) {
+        if (v->isArray || v->isString || (v->raw != "true" && v->raw != "false")) {
+            g_createError = "config parse error: [render] geometryMotion must be true or false";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->geomMotion = v->raw == "true";
+    }
     ctx->bvhSkipPublish = (uint32_t)rttoml::find_or_int(doc, "debug", "bvhSkipPublish", -1);
     ctx->bvhSkipBuilds = rttoml::find_or_int(doc, "debug", "bvhSkipPublishBuilds", -1);
     ctx->bvhWaitMs = rttoml::find_or_float(doc, "debug", "bvhWaitMs", 1000.0f);
@@ -503,6 +511,7 @@ int rt_init(rt_context* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->dCornerSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomSrc, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomDone, hipEventDisableTiming));
+    if (ctx->geomMotion && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;  // [render] geometryMotion
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->inited = true;
     // CameraSetup (init.cu:433-435): a missing or short file leaves the default camera, and the
@@ -671,6 +680,29 @@ int rt_build_bvh(rt_context* ctx) {
     if (ctx->bvhSkipBuilds > 0) --ctx->bvhSkipBuilds;
     p.buildSeq = ++ctx->buildSeq;
     HIP_TRY(ctx, rtk_launch_build_bvh(&p, stream));
+    // geometry motion vectors: a build at another epoch than the previous build's records the
+    // vertices' step between the two, right behind the build and ahead of buildDone, so that the
+    // next update (which overwrites dVerts / dPrevVerts) is behind this read as it is behind the
+    // gather.  The first build, a build at the previous one's epoch and a build whose predecessor's
+    // positions were not kept (the feature was off) record none.
+    {
+        const int k = ctx->bvhSet;
+        ctx->dispValid[k] = false;
+        if (ctx->geomMotion && ctx->built && ctx->geomEpoch != ctx->builtEpoch && ctx->prevVertsValid &&
+            ctx->prevVertsEpoch == ctx->builtEpoch) {
+            GeomDispParams d;
+            d.vertices = ctx->dVerts;
+            d.prevVerts = ctx->dPrevVerts;
+            d.indices = ctx->dIdx;
+            d.triDisp = ctx->bvh[k].triDisp;
+            d.triCountPadded = ctx->mesh.triCountPadded;
+            HIP_TRY(ctx, rtk_launch_geometry_displacement(&d, stream));
+            ctx->dispValid[k] = true;
+            ctx->dispTraced[k] = false;
+        }
+        ctx->built = true;
+        ctx->builtEpoch = ctx->geomEpoch;
+    }
     if (ctx->postStream) {
         HIP_TRY(ctx, hipEventRecord(ctx->buildDone[ctx->bvhSet], stream));
         ctx->buildOnSide[ctx->bvhSet] = true;
@@ -714,7 +746,15 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
     p.contrib = ctx->dContrib;
     p.nverts = ctx->nv;
     p.triCountPadded = ctx->mesh.triCountPadded;
+    // geometry motion vectors: the first update after a build keeps the positions that build gathered
+    // (several updates before the next build count as one step); rt_time_stage(5) keeps nothing
+    const bool keep = bump && ctx->geomMotion && ctx->built && ctx->geomEpoch == ctx->builtEpoch;
+    p.prevVerts = keep ? ctx->dPrevVerts : nullptr;
     HIP_TRY(ctx, rtk_launch_geometry_update(&p, u));
+    if (keep) {
+        ctx->prevVertsValid = true;
+        ctx->prevVertsEpoch = ctx->geomEpoch;
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->geomDone, u));
     ctx->geomStream = u;
     ctx->geomDoneValid = true;
@@ -761,6 +801,41 @@ int rt_update_vertices(rt_context* ctx, const float* xyz, uint32_t first, uint32
 int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch) {
     if (!ctx || !epoch) return RT_ERR_ARG;
     *epoch = ctx->geomEpoch;
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- geometry motion vectors
+//
+// The previous-position array and the displacement records of the LBVH sets that exist (the second
+// set's are allocated with it, ensure_bvh_pair); once allocated they stay.
+int ensure_geometry_motion(rt_context* ctx) {
+    if (!ctx->dPrevVerts) {
+        if (int rc = dalloc(ctx, &ctx->dPrevVerts, (size_t)ctx->nv * 12)) return rc;
+    }
+    for (BvhBufs& b : ctx->bvh)
+        if (b.nodes && !b.triDisp) {
+            if (int rc = dalloc(ctx, &b.triDisp, (size_t)ctx->mesh.triCountPadded * 48)) return rc;
+        }
+    return RT_OK;
+}
+
+int rt_set_geometry_motion(rt_context* ctx, int on) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_set_geometry_motion before rt_init"; return RT_ERR_STATE; }
+    int rc = sync_streams(ctx, false);
+    if (rc != RT_OK) return rc;
+    if (on && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;
+    if ((on != 0) != ctx->geomMotion) {  // from the next build on: what the sets hold is dropped either way
+        ctx->prevVertsValid = false;
+        ctx->dispValid[0] = ctx->dispValid[1] = false;
+    }
+    ctx->geomMotion = on != 0;
+    return RT_OK;
+}
+
+int rt_get_geometry_motion(const rt_context* ctx, int* on) {
+    if (!ctx || !on) return RT_ERR_ARG;
+    *on = ctx->geomMotion ? 1 : 0;
     return RT_OK;
 }
 

@@ -40,6 +40,7 @@ struct BvhBufs {
     uint32_t* tlasReorder = nullptr;
     void* tlasNodes = nullptr;
     uint32_t* counter = nullptr;
+    float4* triDisp = nullptr;  // geometry motion vectors: the records' corner displacements (allocated on enable)
 };
 
 // G-buffer sets in flight with frame pipelining: with four, frame f+4's camera rays wait for the
@@ -291,6 +292,18 @@ struct rt_context {
     uint32_t* dCornerSlot = nullptr;    // corner -> slot in the vertex -> corner CSR (dAdjCorner's inverse)
     float* dContrib = nullptr;          // the corners' normal contributions in CSR order (geometry.hip)
     float* dVertStage = nullptr;        // rt_update_vertices' host positions / rt_time_stage(5)'s copy
+    // geometry motion vectors (rt_set_geometry_motion): the motion buffer of the first
+    // path trace on a build follows the vertices' displacement since the previous build.  dPrevVerts
+    // is written by the first update after a build (k_geom_vertices) and read by the displacement
+    // kernel behind the next build, dVerts' own readers and writers: the same orderings cover it.
+    bool geomMotion = false;            // [render] geometryMotion / rt_set_geometry_motion
+    float* dPrevVerts = nullptr;        // the whole mesh's positions at epoch prevVertsEpoch
+    bool prevVertsValid = false;        // ... saved while the feature was on
+    uint64_t prevVertsEpoch = 0;
+    bool built = false;                 // an LBVH has been built, at geometry epoch builtEpoch (the last build's)
+    uint64_t builtEpoch = 0;
+    bool dispValid[2] = {false, false};   // set k's build recorded a displacement (bvh[k].triDisp)
+    bool dispTraced[2] = {false, false};  // ... and a path trace has applied it: later ones on that build do not
     // frame pipelining: rt_denoise_post(f) is enqueued on the post stream only once the next
     // path trace has enqueued kernel `overlapAfter` (so it fills the trace stages' idle tails), or
     // at the next host read / denoise call, whichever comes first
@@ -375,6 +388,7 @@ extern "C" int copy_rgba_out(rt_context* ctx, void* dst);  // frame.cpp: the las
 extern "C" size_t rt_alloc_bytes(const rt_context* ctx, int name);  // frame.cpp: allocated size of a render buffer
 extern "C" void bvh_select(rt_context* ctx, int k);  // context.cpp: point the dTriPos.. views at bvh[k]
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
+extern "C" int ensure_geometry_motion(rt_context* ctx);  // context.cpp: dPrevVerts and the existing LBVH sets' triDisp
 std::string rt_data_dir();
 void rt_camera_update(const rt_camera& in, int renderW, int renderH, HostCamera& c);
 void rt_input_control_update(rt_context* ctx, float deltaTime);  // input.cpp

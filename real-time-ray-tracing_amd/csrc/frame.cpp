@@ -692,6 +692,9 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.bluenoise = ctx->dBlueNoise;
     p.triPos = ctx->dTriPos;
     p.triNrm = ctx->dTriNrm;
+    // geometry motion vectors: the displacement this LBVH set's build recorded, for the first path
+    // trace on it (rt_path_trace marks it traced); null: the launch sequence has no motion kernel
+    p.triDisp = ctx->dispValid[ctx->bvhSet] && !ctx->dispTraced[ctx->bvhSet] ? ctx->bvh[ctx->bvhSet].triDisp : nullptr;
     p.nodes = ctx->dNodes;
     p.tlasNodes = ctx->dTlasNodes;
     p.texAlbedo = fr.texAlbedo;
@@ -757,6 +760,8 @@ bool spec_matches(const PathTraceParams& a, uint64_t epochA, const PathTracePara
         q->nodes = q->tlasNodes = nullptr;  // the two LBVH sets of one geometry epoch (above)
         q->triPos = nullptr;
         q->triNrm = nullptr;
+        // triDisp stays: launches ahead never carry one (their frame's own path trace came first),
+        // and a launch that does must run its motion kernel
         q->ws.traceBlocks = 0;
         q->ws.shadeBlocksPerCu = 0;  // the shade's grid (dynamic claims: the same result on any grid)
         q->ws.countersZeroed = 0;
@@ -916,6 +921,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     // pending only once the launches that store it are enqueued: a failed launch leaves the next
     // serial frame to ask again instead of freezing the chain choice
     if (askQ3) fr.q3Pending = true;
+    if (p.triDisp) ctx->dispTraced[ctx->bvhSet] = true;  // later path traces on this build see no motion of the geometry
     if (!ctx->postStream) {  // block b + 2 is zeroed by this frame's resolve, enqueued above
         const int b = fr.syncIdx;
         fr.syncZeroed[(b + 2) % 3] = true;
@@ -1349,6 +1355,7 @@ int ensure_bvh_pair(rt_context* ctx) {
             b.triPos = (float4*)((char*)b.nodes + (B * 1024 + B) * 64);
         }
         ALLOC(b.triNrm, NP * 48);
+        if (ctx->geomMotion) ALLOC(b.triDisp, NP * 48);  // else with rt_set_geometry_motion (ensure_geometry_motion)
         ALLOC(b.aabbs, NP * 24);
         ALLOC(b.batchScene, B * 24);
         ALLOC(b.morton, B * 4096);

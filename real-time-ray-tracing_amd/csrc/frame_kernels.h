@@ -199,6 +199,9 @@ struct PathTraceParams {
     uint4* statsOut;            // optional [W*H] rays, node visits, triangle tests, diffuse events
     unsigned long long* rayCounter;  // optional: total traced rays, kRayCounterSlots partial sums
     PtWorkspace ws;
+    // optional [triCountPadded][3] (geometry motion vectors, GeomDispParams::triDisp): set, the shade
+    // kernel is followed by k_pt_geom_motion, which rewrites the motion of the pixels whose sample 0 hit
+    const float4* triDisp;
 };
 
 // TemporalSpatialDenoising + PostProcessing + CopyToOutput (denoise.hip)

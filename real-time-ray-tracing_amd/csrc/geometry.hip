@@ -12,7 +12,11 @@
 //                     weights, the three products pnma * w_k stored at the corners' CSR slots
 //   k_geom_vertices   one thread per vertex: the sum of its slots [adjOff[v], adjOff[v+1]) in order,
 //                     twice, acc = acc + c as k_smooth_normals associates it; it also stores the
-//                     vertex's new position
+//                     vertex's new position (and, for geometry motion vectors, first keeps the
+//                     old one: GeomUpdateParams::prevVerts)
+//
+// and, behind an LBVH build, k_geom_displacement turns the kept positions into the build's
+// displacement records (below; rt_set_geometry_motion).
 //
 // The contributions are kept in CSR order: the scattered side is then the triangle
 // pass's stores, which no wave waits for, and the vertex pass reads one contiguous run per thread,
@@ -71,16 +75,44 @@ __global__ __launch_bounds__(256) void k_geom_vertices(GeomUpdateParams P) {
         }
     float* n = P.normals + 3 * (size_t)vtx;
     n[0] = acc.x; n[1] = acc.y; n[2] = acc.z;
+    float* v = P.vertices + 3 * (size_t)vtx;
+    if (P.prevVerts) {  // the position this update replaces, or keeps: the last build's (geometry motion)
+        float* q = P.prevVerts + 3 * (size_t)vtx;
+        q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+    }
     const uint32_t r = vtx - P.first;
     if (r < P.count) {
         const float* s = P.src + 3 * (size_t)r;
-        float* v = P.vertices + 3 * (size_t)vtx;
         v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    }
+}
+
+// Geometry motion vectors: one thread per triangle record of the LBVH set just built, the three
+// corners' displacement since the previous build.  The records are in the mesh's triangle order (the
+// build gathers triangle g into record g and sorts leaf indices, not records), so record t's
+// corners are indices[3t ..]; a vertex no update touched has prevVerts == vertices bit for bit and
+// the difference is +0.  Per corner one index load and two 12-byte gathers behind it, per thread
+// three 16-byte stores, consecutive threads' stores adjoining: memory-bound, no LDS, no atomics.
+__global__ __launch_bounds__(256) void k_geom_displacement(GeomDispParams P) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= P.triCountPadded) return;
+    const uint32_t* ip = P.indices + 3 * (size_t)t;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t i = ip[k];
+        const float* c = P.vertices + 3 * (size_t)i;
+        const float* q = P.prevVerts + 3 * (size_t)i;
+        P.triDisp[3 * (size_t)t + k] = make_float4(c[0] - q[0], c[1] - q[1], c[2] - q[2], 0.0f);
     }
 }
 
 extern "C" hipError_t rtk_launch_geometry_update(const GeomUpdateParams* p, hipStream_t stream) {
     hipLaunchKernelGGL(k_geom_triangles, dim3((p->triCountPadded + 255) / 256), dim3(256), 0, stream, *p);
     hipLaunchKernelGGL(k_geom_vertices, dim3((p->nverts + 255) / 256), dim3(256), 0, stream, *p);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_geometry_displacement(const GeomDispParams* p, hipStream_t stream) {
+    hipLaunchKernelGGL(k_geom_displacement, dim3((p->triCountPadded + 255) / 256), dim3(256), 0, stream, *p);
     return hipGetLastError();
 }

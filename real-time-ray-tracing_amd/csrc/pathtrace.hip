@@ -848,6 +848,53 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
     add_rays(P, wgRays, raysWg, wS);
 }
 
+// Geometry motion vectors (rt_set_geometry_motion): behind k_pt_shade0, on its
+// stream, when the traced LBVH set carries a displacement no path trace has applied yet (P.triDisp).
+// One thread per entry of the surface list, grid-stride.  A pixel whose sample 0 hit triangle record
+// k at (u, v) was somewhere else in the previous frame: the hit position less the corners'
+// displacement interpolated as finalize_hit interpolates the shading normal,
+//   prev = pos - (d3 (1 - u - v) + d1 u + d2 v),
+// and its motion vector is gbuffer_step0's with prev in place of pos.  The ray and the position are
+// the shade kernel's: start_sample and finalize_hit on sample 0's hit record, the same device
+// functions under the same -ffp-contract=off, so a triangle that did not move (d = +0, prev = pos
+// bit for bit) gets the camera-only value the shade kernel has just stored.  A pixel whose sample 0
+// missed keeps that value, (0.5, 0.5), and all-sky pixels are not on the list.
+// hit0Rec's planes become queue 4's records in forked plans (frame.cpp): this kernel ends, like the
+// shade kernel, before anything the rest of the chain waits for.
+__global__ __launch_bounds__(256) void k_pt_geom_motion(PathTraceParams P) {
+    __shared__ uint32_t sob[256];
+    const int tid = threadIdx.x;
+    bn_stage_sobol(P.bluenoise, sob, tid, 256);
+    __syncthreads();
+    const uint32_t n = P.ws.counters[kCntSurface];
+    const SceneView sc = scene_of(P);
+#pragma unroll 1
+    for (uint32_t i = blockIdx.x * 256u + (uint32_t)tid; i < n; i += gridDim.x * 256u) {
+        const uint32_t pl = P.ws.surface[i];
+        const float4 hr = P.ws.hit0Rec[pl];  // sample 0: plane 0
+        const int tri = (int)__float_as_uint(hr.y);
+        if (!(hr.x < kRayMax) || tri < 0) continue;
+        const int x = (int)(pl % P.width), yl = (int)(pl / P.width);
+        const int y = (int)row_of(P.y0, P.nStrips, P.strip, (uint32_t)yl);
+        const uint32_t p = (uint32_t)y * P.width + (uint32_t)x;
+        PathCtx c = path_ctx(P, sob, nullptr, nullptr);
+        c.bp = bn_pixel(P.bluenoise, x, y);
+        c.frameIdx = (int)P.spp * (P.frameNum - 1) + 1;
+        PathVars v;
+        start_sample(c, v, x, y, 0.0f, f3(0.0f));  // the cone and the centre direction do not reach the ray
+        HitInfo h;
+        finalize_hit(sc, v.rs.orig, v.rs.dir, hr.x, tri, hr.z, hr.w, P.ws.hit0Err[pl], h);
+        const F3 d1 = f3_of(P.triDisp[3 * tri]), d2 = f3_of(P.triDisp[3 * tri + 1]), d3 = f3_of(P.triDisp[3 * tri + 2]);
+        v.rs.pos = h.pos - (d3 * (1.0f - hr.z - hr.w) + d1 * hr.z + d2 * hr.w);
+        v.rs.hit = true;
+        v.rs.depth = h.t;
+        gbuffer_step0(c, v);
+        F2 M = v.mv;
+        if (M.x != M.x || M.y != M.y) M = F2{0.0f, 0.0f};  // as the shade kernel stores a NaN
+        P.motionOut[p] = (uint32_t)rt_f2h(M.x) | ((uint32_t)rt_f2h(M.y) << 16);
+    }
+}
+
 // run_path<0, kMF>(c, v, kStep, &hit, ..) in straight line where no glossy interaction can run:
 // step 4 (it ends the path) for any table, step 3 without mirror or glass (as run_shade0_diffuse:
 // G3 returns at once, so step 3 is D1 and step 4 traces exactly when D1 produced a ray)
@@ -1315,9 +1362,15 @@ void launch_shade_rounds(const PathTraceParams* p, hipStream_t stream) {
     }
 }
 
+// The shade kernel and, when the launch carries a displacement (geometry motion vectors), the motion
+// kernel right behind it: one slot for the marks and the hook, so the kernel numbers keep their meaning
 void launch_shade(const PathTraceParams* p, hipStream_t stream) {
     if (one_round(p->spp)) launch_shade_rounds<true>(p, stream);
     else launch_shade_rounds<false>(p, stream);
+    if (p->triDisp) {  // the list's length is known on the device only: a grid-stride loop over at most 8 workgroups per CU
+        const uint32_t need = (p->rows * p->width + 255u) / 256u, cap = 8u * (p->ws.cus ? p->ws.cus : 256u);
+        hipLaunchKernelGGL(k_pt_geom_motion, dim3(need < cap ? need : cap), dim3(256), 0, stream, *p);
+    }
 }
 
 hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks, const PtLaunchHook* hook,

@@ -152,6 +152,8 @@ SIGNATURES = {
     "rt_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rt_get_geometry_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_set_geometry_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_get_geometry_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 IMAGE_PPM_RGBA8, IMAGE_PFM_HDR = 0, 1
 DRAW_ASYNC = 1  # rt_draw_device flag
@@ -192,12 +194,15 @@ class RtError(RuntimeError):
 
 def write_config(path: str, width: int, height: int, dynamic: bool = False, chunk_dim: int = 1, spp: int = 1,
                  extra: str = "", max_size=(3840, 2160), camera_file: str | None = None, min_size=(640, 480),
-                 target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None) -> str:
+                 target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None,
+                 geometry_motion: bool | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
     RTX_TUNING environment variable ("key=value,key=value", e.g. "chain=off,tracePerCu=2") fills
-    it: the A/B tools (tools/ab.sh) set it per variant.  The library itself reads no environment."""
+    it: the A/B tools (tools/ab.sh) set it per variant.  The library itself reads no environment.
+    `geometry_motion`: [render] geometryMotion, the initial state of rt_set_geometry_motion (None:
+    the key is not written, the default is off)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -212,6 +217,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
         if mesh_file:  # a meshProcessor .bin instead of the procedural terrain (init.cu:28-50)
             f.write('meshFile = "%s"\n' % mesh_file)
         f.write("\n[render]\nspp = %d\n" % spp)
+        if geometry_motion is not None:
+            f.write("geometryMotion = %s\n" % ("true" if geometry_motion else "false"))
         f.write(extra)
         if tuning is None:
             tuning = tuning_from_env()
@@ -361,6 +368,17 @@ class RayTracer:
         v = C.c_uint64()
         self._check(self.lib.rt_get_geometry_epoch(self.h, C.byref(v)), "rt_get_geometry_epoch")
         return v.value
+
+    @property
+    def geometry_motion(self) -> bool:
+        """Geometry motion vectors (rt_set_geometry_motion): the MOTION G-buffer follows vertex updates."""
+        v = C.c_int()
+        self._check(self.lib.rt_get_geometry_motion(self.h, C.byref(v)), "rt_get_geometry_motion")
+        return bool(v.value)
+
+    @geometry_motion.setter
+    def geometry_motion(self, on: bool):
+        self._check(self.lib.rt_set_geometry_motion(self.h, 1 if on else 0), "rt_set_geometry_motion")
 
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")

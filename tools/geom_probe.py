@@ -7,7 +7,15 @@ scene, HIP-event medians of
 
 one launch per sample in the same process, the compulsory bytes of (b) against the HBM peak, and the
 pipelined 1080p 4-spp frame time with a whole-mesh update every frame (with a ready event, without
-one) beside the same loop without updates.  Writes profiles/geom_update.json.
+one) beside the same loop without updates.  Geometry motion vectors (rt_set_geometry_motion) add
+
+  (c) k_geom_displacement alone (rtk_launch_geometry_displacement on the context's own arrays),
+  (d) the shade kernel's mark slot of a serial 1080p frame on moved geometry with the feature on and
+      off, same process, frame by frame in turn: k_pt_geom_motion has no slot of its own, it is the
+      difference, and
+  (e) the pipelined loop with a ready event again with the feature on, beside the run with it off.
+
+Writes profiles/geom_update.json.
 
 Usage: python tools/geom_probe.py [--samples 40] [--repeats 5] [--frames 200] [--out PATH]"""
 import argparse
@@ -104,44 +112,132 @@ def stage_times(rtx, torch, chunk, samples, repeats):
                 samples_per_median=samples)
 
 
-def frame_times(rtx, torch, chunk, frames, warmup=30):
-    """ms per pipelined 1080p 4-spp frame: no updates / an update per frame with a ready event / without."""
+class GeomDispParams(C.Structure):  # csrc/bvh_kernels.h
+    _fields_ = [("vertices", C.c_void_p), ("prevVerts", C.c_void_p), ("indices", C.c_void_p), ("triDisp", C.c_void_p),
+                ("triCountPadded", C.c_uint32)]
+
+
+def motion_times(rtx, torch, chunk, samples, repeats):
+    """(c) and (d) on the scene of [scene] chunkDim `chunk`."""
+    dev = torch.device("cuda", 0)
+    w, h = 1920, 1080
+    cfg = lambda name, on: rtx.write_config(os.path.join(tempfile.mkdtemp(), name), w, h, spp=4, chunk_dim=chunk,
+                                            geometry_motion=on)
+    rts = {on: rtx.RayTracer(w, h, cfg("m%d.toml" % on, on)).init() for on in (True, False)}
+    rt = rts[True]
+    info = rt.info()
+    nv, NP = int(info.vertexCount), int(info.triCountPadded)
+    v = rt.download("VERTICES", np.float32).reshape(-1, 3)
+    v2 = v.copy()
+    v2[:, 1] += np.float32(0.05) * np.sin(np.float32(3) * v[:, 0] + np.float32(2) * v[:, 2])
+    idx = rt.download("INDICES", np.uint32)
+    dcur, dprev, di = (torch.from_numpy(a).to(dev) for a in (v2, v, idx.view(np.int32)))
+    ddisp = torch.zeros(NP * 12, dtype=torch.float32, device=dev)
+    launch = rt.lib.rtk_launch_geometry_displacement
+    launch.restype = C.c_int
+    launch.argtypes = [C.POINTER(GeomDispParams), C.c_void_p]
+    prm = GeomDispParams(dcur.data_ptr(), dprev.data_ptr(), di.data_ptr(), ddisp.data_ptr(), NP)
+    stream = torch.cuda.Stream(dev)
+    med_c = []
+    for _ in range(repeats):
+        ms = []
+        for k in range(samples + 5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            assert launch(C.byref(prm), stream.cuda_stream) == 0
+            e1.record(stream)
+            e1.synchronize()
+            if k >= 5:
+                ms.append(e0.elapsed_time(e1))
+        med_c.append(float(np.median(ms)))
+    d = ddisp.cpu().numpy().reshape(NP, 3, 4)
+    want = (v2[idx.reshape(-1, 3)] - v[idx.reshape(-1, 3)])
+    disp_ok = bool(np.array_equal(d[:, :, :3], want) and not d[:, :, 3].any())
+    # (d): serial frames, the geometry alternating between v and v2, the shade slot marked
+    pos = [torch.from_numpy(a).to(dev) for a in (v, v2)]
+    torch.cuda.synchronize()
+    slot = {True: [], False: []}
+    for f in range(1, samples + 6):
+        for on in (True, False):
+            r = rts[on]
+            r.set_delta_time(16.667)
+            r.update_vertices_device(pos[f & 1].data_ptr(), nv, 0, None)
+            r.build_bvh()
+            r.frame_marks_begin(1, ["k_pt_shade0"])
+            r.path_trace(f)
+            r.denoise_post(f)
+            ms, n = r.frame_marks_read()
+            assert n == 1
+            if f > 5:
+                slot[on].append(ms["k_pt_shade0"])
+    same = bool(np.array_equal(rts[True].get_buffer("RENDER_COLOR"), rts[False].get_buffer("RENDER_COLOR")))
+    for r in rts.values():
+        r.cleanup()
+    on_ms, off_ms = float(np.median(slot[True])), float(np.median(slot[False]))
+    c = float(np.median(med_c))
+    nbytes = NP * 12 + 2 * 3 * NP * 12 + NP * 48  # indices, two gathered positions per corner, the records
+    return dict(chunk_dim=chunk, triangles_padded=NP, vertices=nv, c_displacement_ms=c, c_medians_ms=med_c,
+                c_bytes=nbytes, c_fraction_of_hbm_peak=nbytes / (c * 1e-3) / HBM_PEAK, c_bits_equal_numpy=disp_ok,
+                d_shade_slot_motion_on_ms=on_ms, d_shade_slot_motion_off_ms=off_ms, d_motion_kernel_ms=on_ms - off_ms,
+                d_config="1920x1080, 4 spp, serial staged frames, whole-mesh update per frame, median of %d frames" % samples,
+                d_denoised_frames_differ=not same, samples_per_median=samples)
+
+
+def frame_times(rtx, torch, chunk, frames, warmup=30, repeats=5):
+    """ms per pipelined 1080p 4-spp frame: no updates / an update per frame with a ready event / without /
+    with a ready event and geometry motion vectors on.  One context per mode in the same process, the
+    modes timed in turn `repeats` times (`frames` frames each, after `warmup` frames once): medians, so
+    that a drift of the box's clocks falls on every mode alike."""
     from rtx.frames import FramePipeline
 
     w, h = 1920, 1080
     dev = torch.device("cuda", 0)
-    out = {}
-    for mode in ("none", "ready_event", "null_event"):
-        rt = rtx.RayTracer(w, h, rtx.write_config(os.path.join(tempfile.mkdtemp(), "f.toml"), w, h, spp=4, chunk_dim=chunk)).init()
-        rt.set_delta_time(16.667)
-        v = rt.download("VERTICES", np.float32).reshape(-1, 3)
-        v2 = v.copy()
-        v2[:, 1] += np.float32(0.05) * np.sin(np.float32(3) * v[:, 0] + np.float32(2) * v[:, 2])
-        pos = [torch.from_numpy(a).to(dev) for a in (v, v2)]
-        anim = torch.cuda.Stream(dev)
-        ev = torch.cuda.Event()
-        ev.record(anim)  # the host's animation stream has produced both arrays
-        torch.cuda.synchronize()
-        prev = torch.cuda.current_stream(0)
-        fp = FramePipeline(rt, dev, pipelined=True)
-        try:
-            t0 = 0.0
-            for f in range(1, warmup + frames + 1):
-                if f == warmup + 1:
-                    fp.finish()
-                    t0 = time.perf_counter()
+    modes = ("none", "ready_event", "null_event", "ready_event_motion")
+    prev = torch.cuda.current_stream(0)
+    ctx, series = {}, {m: [] for m in modes}
+    try:
+        for mode in modes:
+            rt = rtx.RayTracer(w, h, rtx.write_config(os.path.join(tempfile.mkdtemp(), "f.toml"), w, h, spp=4, chunk_dim=chunk,
+                                                      geometry_motion=mode == "ready_event_motion")).init()
+            rt.set_delta_time(16.667)
+            v = rt.download("VERTICES", np.float32).reshape(-1, 3)
+            v2 = v.copy()
+            v2[:, 1] += np.float32(0.05) * np.sin(np.float32(3) * v[:, 0] + np.float32(2) * v[:, 2])
+            pos = [torch.from_numpy(a).to(dev) for a in (v, v2)]
+            anim = torch.cuda.Stream(dev)
+            ev = torch.cuda.Event()
+            ev.record(anim)  # the host's animation stream has produced both arrays
+            torch.cuda.synchronize()
+            ctx[mode] = dict(rt=rt, pos=pos, ev=ev, fp=FramePipeline(rt, dev, pipelined=True), f=0)
+
+        def run(mode, n):
+            c = ctx[mode]
+            for _ in range(n):
+                c["f"] += 1
                 if mode == "none":
-                    fp.frame(f)
+                    c["fp"].frame(c["f"])
                 else:
-                    fp.frame(f, vertices=pos[f & 1], vertices_ready=ev if mode == "ready_event" else None)
-            fp.finish()
-            out[mode + "_ms_per_frame"] = (time.perf_counter() - t0) * 1e3 / frames
-        finally:
-            rt.cleanup()
-            torch.cuda.set_stream(prev)
+                    c["fp"].frame(c["f"], vertices=c["pos"][c["f"] & 1], vertices_ready=None if mode == "null_event" else c["ev"])
+            c["fp"].finish()
+
+        for mode in modes:
+            run(mode, warmup)
+        for _ in range(repeats):
+            for mode in modes:
+                t0 = time.perf_counter()
+                run(mode, frames)
+                series[mode].append((time.perf_counter() - t0) * 1e3 / frames)
+    finally:
+        for c in ctx.values():
+            c["rt"].cleanup()
+        torch.cuda.set_stream(prev)
+    out = {m + "_ms_per_frame": float(np.median(series[m])) for m in modes}
+    out.update({m + "_series_ms": series[m] for m in modes})
     out["animation_cost_ready_event_ms"] = out["ready_event_ms_per_frame"] - out["none_ms_per_frame"]
     out["animation_cost_null_event_ms"] = out["null_event_ms_per_frame"] - out["none_ms_per_frame"]
-    out.update(chunk_dim=chunk, frames=frames, config="1920x1080, 4 spp, pipelined FramePipeline, whole-mesh update per frame")
+    out["motion_cost_ready_event_ms"] = out["ready_event_motion_ms_per_frame"] - out["ready_event_ms_per_frame"]
+    out.update(chunk_dim=chunk, frames=frames, repeats=repeats,
+               config="1920x1080, 4 spp, pipelined FramePipeline, whole-mesh update per frame")
     return out
 
 
@@ -161,6 +257,7 @@ def main():
                method="HIP events around one launch per sample, median of --samples after 5 warm-up launches, "
                       "repeated --repeats times with (a) and (b) interleaved; the margin is the spread of (a)'s medians",
                stages=[stage_times(rtx, torch, c, a.samples, a.repeats) for c in (1, 4)],
+               motion=[motion_times(rtx, torch, c, a.samples, a.repeats) for c in (1, 4)],
                frames=[frame_times(rtx, torch, c, a.frames) for c in (1, 4)])
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
