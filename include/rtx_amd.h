@@ -559,6 +559,47 @@ int rt_download(const rt_context* ctx, int what, void* dst, size_t bytes);
  *   kernel_ms optional: HIP-event time of the tracer kernel alone
  * n must not exceed width x strip rows x spp (the queue capacity).  Host buffers; synchronous. */
 int rt_trace_rays(rt_context* ctx, const float* rays, uint32_t n, float* hits, uint32_t* iters, float* kernel_ms);
+
+/* Device ray queries (no reference counterpart): the same traversal for rays and results that live
+ * in caller-owned device memory, stream-ordered like rt_update_vertices_device.  For hosts that keep
+ * their data on the stream given to rt_set_stream: visibility, line of sight, picking, collision,
+ * ray-cast sensors against the geometry they just animated, between pipelined frames.
+ *
+ * Records: flags 0 gives the closest hit, equal to rt_trace_rays' record (and iteration count) for
+ * the same ray bit for bit.  RT_QUERY_ANY_HIT ends each ray at the iteration in which the traversal
+ * first records a hit, and the record is that hit: same hit / miss answer as the closest-hit query,
+ * t >= the closest t, fewer iterations.  There is no tmin / tmax: every ray starts at t = RayMax (a
+ * shorter initial t changes which pushes the traversal's 16-entry stack drops, and with them the
+ * record, so it would be another traversal than the reference's).  n is not limited by the queue
+ * capacity, only by RT_QUERY_MAX_RAYS.  n == 0 is RT_OK and enqueues nothing but done_event.
+ *
+ * Ordering: asynchronous, the host is never synchronised; no stream is drained, what a synchronous
+ * draw traced ahead is kept, and the path tracer's workspace, RT_ARR_PT_QUEUE and rt_get_ray_count
+ * are left as they were.  The kernel runs on the context stream (rt_set_stream), after ready_event
+ * if one is given (a hipEvent_t; NULL: the inputs are read after everything enqueued on the context
+ * stream so far).  It traces the BVH of the last rt_build_bvh, explicit or inside a draw, enqueued
+ * before the call, waits for that build wherever it ran, and holds that LBVH set against every
+ * later build that would overwrite it.  The results are visible to work enqueued on the context
+ * stream after the call and to whatever waits for done_event (a hipEvent_t the call records behind
+ * the kernel, or NULL).  All buffers must stay valid, and the inputs unchanged, until then.
+ *
+ * RT_ERR_ARG: NULL ctx or q (checked first); then, before the init state: a stride below 3,
+ * n > RT_QUERY_MAX_RAYS, unknown flag bits, and with n > 0 a NULL org, dir or hits, hits not 16-byte
+ * aligned, org, dir or iters not 4-byte aligned.  RT_ERR_STATE before rt_init; RT_ERR_HIP for a
+ * failed launch.  Like the setters it never returns RT_ERR_DEVICE. */
+#define RT_QUERY_ANY_HIT 1u            /* stop each ray at the first hit the traversal accepts */
+#define RT_QUERY_MAX_RAYS (1u << 30)   /* keeps the kernel's fetch arithmetic inside 32 bits */
+typedef struct rt_ray_query {
+    const float* org;  uint32_t org_stride;   /* device; stride in floats, >= 3 (3: packed xyz, 8: rt_trace_rays' layout) */
+    const float* dir;  uint32_t dir_stride;   /* device; same rules; need not be normalised (as rt_trace_rays) */
+    uint32_t n;
+    float* hits;        /* device, 16-B aligned, n x 4: t (RayMax on a miss), triangle index as int32 bits (-1), u, v */
+    uint32_t* iters;    /* device, optional: TraverseBvh iterations per ray */
+    uint32_t flags;     /* 0 or RT_QUERY_ANY_HIT */
+    void* ready_event;  /* hipEvent_t or NULL, as in rt_update_vertices_device */
+    void* done_event;   /* hipEvent_t or NULL: recorded on the context stream behind the kernel */
+} rt_ray_query;
+int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q);
 size_t rt_array_bytes(const rt_context* ctx, int what);
 
 #ifdef __cplusplus

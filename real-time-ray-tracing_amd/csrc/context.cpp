@@ -511,6 +511,10 @@ int rt_init(rt_context* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->dCornerSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomSrc, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomDone, hipEventDisableTiming));
+    // device ray queries (rt_trace_rays_device): their fetch counters and events, so that a query only enqueues work
+    if ((rc = dalloc(ctx, &ctx->queryFetch, 512)) != RT_OK) return rc;
+    for (hipEvent_t* e : {&ctx->queryDone[0], &ctx->queryDone[1]})
+        HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (ctx->geomMotion && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;  // [render] geometryMotion
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->inited = true;
@@ -525,7 +529,7 @@ void rt_destroy(rt_context* ctx) {
     if (!ctx) return;
     if (ctx->inited) (void)sync_streams(ctx, false);  // also when the context stream is the null stream
     for (hipEvent_t e : {ctx->overlapEv, ctx->cameraGate, ctx->specGate, ctx->specDone, ctx->buildDone[0], ctx->buildDone[1],
-                         ctx->bvhFree[0], ctx->bvhFree[1], ctx->geomSrc, ctx->geomDone})
+                         ctx->bvhFree[0], ctx->bvhFree[1], ctx->geomSrc, ctx->geomDone, ctx->queryDone[0], ctx->queryDone[1]})
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kGbSets; ++k)
         for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k],

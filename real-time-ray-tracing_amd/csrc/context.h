@@ -304,6 +304,14 @@ struct rt_context {
     uint64_t builtEpoch = 0;
     bool dispValid[2] = {false, false};   // set k's build recorded a displacement (bvh[k].triDisp)
     bool dispTraced[2] = {false, false};  // ... and a path trace has applied it: later ones on that build do not
+    // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
+    // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
+    // and the setters that change the stream drain it), and on a context without a post stream the
+    // end of the last query that read LBVH set k, which a synchronous draw's prebuild into that set
+    // waits for (a pipelined context records bvhFree[k] instead, as its path traces do)
+    uint32_t* queryFetch = nullptr;
+    hipEvent_t queryDone[2] = {};
+    bool queryInFlight[2] = {false, false};
     // frame pipelining: rt_denoise_post(f) is enqueued on the post stream only once the next
     // path trace has enqueued kernel `overlapAfter` (so it fills the trace stages' idle tails), or
     // at the next host read / denoise call, whichever comes first

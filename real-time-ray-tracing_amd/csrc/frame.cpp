@@ -1132,11 +1132,16 @@ namespace {
 // denoise instead of ahead of the next frame's path trace.  The build depends on nothing this
 // frame computes, only on the geometry: it carries the epoch it gathered (prebuiltEpoch), and a
 // draw that finds another one (a vertex update since) builds again.  The other set was last read
-// by the previous frame, which has finished.
+// by the previous frame, which has finished, or by a device ray query enqueued since
+// (rt_trace_rays_device), which may not have: the side stream waits for the last such query.
 int prebuild_next_bvh(rt_context* ctx) {
     int rc;
     if ((rc = ensure_bvh_pair(ctx)) != RT_OK) return rc;
     const int cur = ctx->bvhSet;
+    if (ctx->queryInFlight[cur ^ 1]) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->queryDone[cur ^ 1], 0));
+        ctx->queryInFlight[cur ^ 1] = false;
+    }
     bvh_select(ctx, cur ^ 1);
     hipStream_t keep = ctx->stream;  // no post stream: rt_build_bvh builds on ctx->stream
     ctx->stream = ctx->sideStream;
@@ -1682,5 +1687,55 @@ int rt_trace_rays(rt_context* ctx, const float* rays, uint32_t n, float* hits, u
     if (iters) HIP_TRY(ctx, hipMemcpyAsync(iters, p.ws.itersOut, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+    return RT_OK;
+}
+
+// Device ray queries (trace_rays.hip): the same traversal for caller rays in device memory, enqueued
+// on the context stream between whatever else the host enqueues there.  Unlike rt_trace_rays it
+// drains nothing, keeps what a synchronous draw traced ahead, and uses none of the path tracer's
+// workspace (fr.ws.counters, the queues, hitRec*, pathL, syncZeroed) nor the ray counter.
+// Check order: NULL ctx / q, then the other argument checks, then the init state.
+int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q) {
+    if (!ctx || !q) return RT_ERR_ARG;
+    const char* bad = nullptr;
+    if (q->org_stride < 3u || q->dir_stride < 3u) bad = "strides are in floats and at least 3";
+    else if (q->n > RT_QUERY_MAX_RAYS) bad = "more rays than RT_QUERY_MAX_RAYS";
+    else if ((q->flags & ~RT_QUERY_ANY_HIT) != 0u) bad = "unknown flags";
+    else if (q->n > 0u && (!q->org || !q->dir || !q->hits)) bad = "org, dir and hits must not be NULL";
+    else if (((uintptr_t)q->hits & 15u) != 0) bad = "hits must be 16-byte aligned";
+    else if ((((uintptr_t)q->org | (uintptr_t)q->dir | (uintptr_t)q->iters) & 3u) != 0) bad = "org, dir and iters must be 4-byte aligned";
+    if (bad) { ctx->err = std::string("rt_trace_rays_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_trace_rays_device before rt_init"; return RT_ERR_STATE; }
+    hipStream_t s = ctx->stream;
+    if (q->n > 0u) {
+        if (q->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)q->ready_event, 0));
+        if (int rc = wait_bvh(ctx)) return rc;  // the current set's build, wherever it ran
+        RayQueryParams p;
+        p.nodes = ctx->dNodes;
+        p.tlasNodes = ctx->dTlasNodes;
+        p.triPos = ctx->dTriPos;
+        p.org = q->org;
+        p.dir = q->dir;
+        p.orgStride = q->org_stride;
+        p.dirStride = q->dir_stride;
+        p.n = q->n;
+        p.hits = reinterpret_cast<float4*>(q->hits);
+        p.iters = q->iters;
+        p.fetch = ctx->queryFetch;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->queryFetch, 0, 512, s));
+        // the queue tracers' grid policy (rt_frame_init: cus x tracePerCu, [tuning] tracePerCu)
+        HIP_TRY(ctx, rtk_launch_trace_rays(&p, ctx->fr.ws.traceBlocks, (q->flags & RT_QUERY_ANY_HIT) != 0u, s));
+        // the set is held against the builds that would overwrite it: a pipelined context's next build
+        // but one (rt_build_bvh waits for bvhFree), a synchronous draw's prebuild (prebuild_next_bvh)
+        const int k = ctx->bvhSet;
+        if (ctx->postStream) {
+            HIP_TRY(ctx, hipEventRecord(ctx->bvhFree[k], s));
+            ctx->bvhInFlight[k] = true;
+        } else {
+            HIP_TRY(ctx, hipEventRecord(ctx->queryDone[k], s));
+            ctx->queryInFlight[k] = true;
+        }
+    }
+    if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));
     return RT_OK;
 }

@@ -328,3 +328,19 @@ extern "C" hipError_t rtk_launch_pt_rest_after_shade(const PathTraceParams* p, h
                                                      const PtLaunchHook* hook, const PtLeanFork* fork);
 extern "C" int rtk_trace_queue_blocks_per_cu();
 extern "C" hipError_t rtk_launch_trace_queue(const PathTraceParams* p, int step, hipStream_t stream);
+
+// One device ray query (trace_rays.hip, rt_trace_rays_device): caller rays in, hit records out
+struct RayQueryParams {
+    const void* nodes;       // the LBVH set's record arena, its TLAS nodes and triangle records
+    const void* tlasNodes;
+    const float4* triPos;
+    const float* org;        // ray i's origin at org + i * orgStride, direction at dir + i * dirStride
+    const float* dir;
+    uint32_t orgStride, dirStride;  // in floats, >= 3
+    uint32_t n;              // 1 .. RT_QUERY_MAX_RAYS
+    float4* hits;            // [n] t, triangle index bits, u, v
+    uint32_t* iters;         // optional [n]
+    uint32_t* fetch;         // [8 parts x 16]: the query's own fetch counters, 64 B apart, zero at launch
+};
+// grid: min(maxBlocks, ceil(n / 256)) workgroups
+extern "C" hipError_t rtk_launch_trace_rays(const RayQueryParams* p, uint32_t maxBlocks, int anyHit, hipStream_t stream);

@@ -95,6 +95,16 @@ class StripExchange(C.Structure):
                 ("gbufferSet", C.c_int32), ("stripLocal", C.c_int32)]
 
 
+class RayQuery(C.Structure):
+    """rt_ray_query: one device ray query (rt_trace_rays_device)."""
+    _fields_ = [("org", C.c_void_p), ("org_stride", C.c_uint32), ("dir", C.c_void_p), ("dir_stride", C.c_uint32),
+                ("n", C.c_uint32), ("hits", C.c_void_p), ("iters", C.c_void_p), ("flags", C.c_uint32),
+                ("ready_event", C.c_void_p), ("done_event", C.c_void_p)]
+
+
+QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
+QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
+
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(StripExchange))
 HOOK_HISTOGRAM, HOOK_ROWS, HOOK_GBUFFERS = 0, 1, 2
 
@@ -138,6 +148,7 @@ SIGNATURES = {
     "rt_time_path_trace_kernels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int]),
     "rt_time_frame_kernels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayQuery)]),
     "rt_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rt_array_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "rt_save_camera": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -528,6 +539,21 @@ class RayTracer:
                     "rt_trace_rays")
         out = (hits[:, 0], hits[:, 1].view(np.int32), hits[:, 2], hits[:, 3])
         return out + ((iters,) if want_iters else ()) + (ms.value,)
+
+    def trace_rays_device(self, org_ptr: int, dir_ptr: int, n: int, hits_ptr: int, *, org_stride: int = 3,
+                          dir_stride: int = 3, iters_ptr: int | None = None, any_hit: bool = False,
+                          ready_event: int | None = None, done_event: int | None = None):
+        """rt_trace_rays_device: n rays from device memory (origin i at org_ptr + 4 * i * org_stride
+        bytes, directions alike) into n (t, triangle bits, u, v) float32 records at hits_ptr, enqueued
+        on the context stream; the host is not synchronised.  ready_event / done_event: hipEvent_t
+        handles (torch.cuda.Event.cuda_event) the kernel waits for / that is recorded behind it.
+        rtx.query.trace is the torch-tensor form."""
+        for name, v in (("n", n), ("org_stride", org_stride), ("dir_stride", dir_stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("trace_rays_device: %s must fit 32 bits" % name)
+        q = RayQuery(org_ptr, int(org_stride), dir_ptr, int(dir_stride), int(n), hits_ptr, iters_ptr,
+                     QUERY_ANY_HIT if any_hit else 0, ready_event, done_event)
+        self._check(self.lib.rt_trace_rays_device(self.h, C.byref(q)), "rt_trace_rays_device")
 
     def get_buffer(self, name: str, shape=None, dtype=np.uint8) -> np.ndarray:
         if shape is None:
