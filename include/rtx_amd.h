@@ -349,6 +349,35 @@ int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch); /* 0 after rt
 int rt_set_geometry_motion(rt_context* ctx, int on);
 int rt_get_geometry_motion(const rt_context* ctx, int* on);
 
+/* Per-triangle materials: SceneMaterial::materialsIdx (kernel.cuh:198-203, init.cu:261-269), the
+ * material id the path tracer looks up at every hit (traverse.cuh:29-32).  ids[k] is the material of
+ * triangle first + k, the objectIdx a hit reports; [first, first + count) lies within triCount
+ * (rt_get_info), the topology being fixed as for rt_update_vertices.  Ids 0..9 index the reference's
+ * material table (0, 2: emissive; 1: glass; 3, 6..9: Lambertian; 4: microfacet; 5: mirror); an id
+ * >= 10 is the reference's out-of-range default, a mirror whose material mask is the id.  The mask
+ * of RT_BUF_COLOR is the id of sample 0's triangle, which the denoiser's *_sigma_material weights
+ * compare.
+ *
+ * Before the first set, and after rt_reset_triangle_materials, the table is the reference's: 3 for
+ * every triangle, and the path trace launches exactly the kernels it launched before this call
+ * existed.  The first set allocates one device byte per triangle (initialised to 3) and a host copy,
+ * from which the census of ids, and with it the kernel variants a frame needs
+ * (rt_material_classes), is taken without a device read.  A table of Lambertian and emissive ids
+ * keeps the default kernels; one mirror or glass triangle puts the frame on the glossy ones.
+ *
+ * Both calls wait for the renderer's streams like the other setters, drop what a synchronous draw
+ * traced ahead, and take effect for every path trace enqueued after them; they are not
+ * stream-ordered.  [render] materialOverride >= 0 still wins over the table.
+ * RT_ERR_ARG: NULL ctx or ids, count == 0, first + count > triCount; RT_ERR_STATE before rt_init;
+ * RT_ERR_HIP: the allocation or the copy failed.  Never RT_ERR_DEVICE. */
+int rt_set_triangle_materials(rt_context* ctx, const uint8_t* ids, uint32_t first, uint32_t count);
+int rt_reset_triangle_materials(rt_context* ctx);
+#define RT_MAT_CLASS_GLOSSY 1u      /* an id whose type is mirror or glass: 1, 5, and every id >= 10 */
+#define RT_MAT_CLASS_MICROFACET 2u  /* id 4 */
+/* The kernel classes of a set of ids (the OR over ids[0..n)); host only, no device or context
+ * needed.  RT_ERR_ARG: classes NULL, or ids NULL with n > 0. */
+int rt_material_classes(const uint8_t* ids, size_t n, uint32_t* classes);
+
 /* BASELINE config 2: GenerateRay + RaySceneIntersect for every render pixel with the
  * blue-noise sample of frame_num (pathtrace.cuh:116-130), enqueued asynchronously.
  * with_detail != 0 also stores normals / shading normals / traversal counters. */
@@ -544,9 +573,11 @@ enum rt_array_name {
     RT_ARR_TEX_NORMAL_ROUGHNESS = 38, /* ushort4, same layout */
     RT_ARR_TEX_HEIGHT = 39,      /* ushort, same layout (zero unless uploaded) */
     RT_ARR_HDR = 40,             /* float4[W*H] pre-tone-map HDR of the last rt_draw / rt_denoise_post with_hdr */
-    RT_ARR_BVH_ARENA = 41        /* the traversal's record arena as the device holds it (64-B records: B*1024 BLAS
+    RT_ARR_BVH_ARENA = 41,       /* the traversal's record arena as the device holds it (64-B records: B*1024 BLAS
                                     nodes, B TLAS nodes, triCountPadded triangle records); the
                                     NODES / TLAS_NODES / TRI_POS arrays are views of it in the reference layout */
+    RT_ARR_TRI_MATERIALS = 42    /* uint8[triCount] material id per triangle (rt_set_triangle_materials); all 3
+                                    before the first set and after a reset */
 };
 int rt_download(const rt_context* ctx, int what, void* dst, size_t bytes);
 

@@ -843,6 +843,76 @@ int rt_get_geometry_motion(const rt_context* ctx, int* on) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- per-triangle materials
+//
+// SceneMaterial::materialsIdx (kernel.cuh:198-203, init.cu:261-269): one material id per triangle,
+// looked up at every hit (traverse.cuh:29-32; update_material in pathtrace.hip).
+
+// Which ids select which kernel class: mat_type (shade.h) gives mirror to id 5 and glass to id 1, and
+// an id past the ten-entry table is the reference's SAFE_LOAD default, mirror; id 4 is the one
+// microfacet material.  The one statement of the rule (fill_pt_params calls it too).
+int rt_material_classes(const uint8_t* ids, size_t n, uint32_t* classes) {
+    if (!classes || (!ids && n)) return RT_ERR_ARG;
+    uint32_t c = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const uint8_t id = ids[k];
+        if (id == 1 || id == 5 || id >= 10) c |= RT_MAT_CLASS_GLOSSY;
+        else if (id == 4) c |= RT_MAT_CLASS_MICROFACET;
+    }
+    *classes = c;
+    return RT_OK;
+}
+
+// the classes of the ids that have a triangle, from the census
+static void census_classes(rt_context* ctx) {
+    uint8_t present[256];
+    size_t n = 0;
+    for (int id = 0; id < 256; ++id)
+        if (ctx->triMatCount[id]) present[n++] = (uint8_t)id;
+    (void)rt_material_classes(present, n, &ctx->triMatClasses);
+}
+
+int rt_set_triangle_materials(rt_context* ctx, const uint8_t* ids, uint32_t first, uint32_t count) {
+    if (!ctx || !ids) return RT_ERR_ARG;
+    if (count == 0) { ctx->err = "rt_set_triangle_materials: count must not be 0"; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_set_triangle_materials before rt_init"; return RT_ERR_STATE; }
+    const uint32_t n = ctx->mesh.triCount;
+    if ((uint64_t)first + (uint64_t)count > (uint64_t)n) {
+        ctx->err = "rt_set_triangle_materials: [first, first + count) must be a non-empty range of the mesh's triangles";
+        return RT_ERR_ARG;
+    }
+    // the kernels in flight read the table, and camera rays traced ahead precede it (spec_matches)
+    if (int rc = sync_streams(ctx, false)) return rc;
+    if (!ctx->triMatStore) {
+        if (int rc = dalloc(ctx, &ctx->triMatStore, (size_t)ctx->mesh.triCountPadded)) return rc;
+    }
+    if (!ctx->dTriMat) {  // the first set, or the first after a reset: the reference's table
+        HIP_TRY(ctx, hipMemset(ctx->triMatStore, 3, (size_t)ctx->mesh.triCountPadded));
+        ctx->triMatHost.assign(n, (uint8_t)3);
+        memset(ctx->triMatCount, 0, sizeof ctx->triMatCount);
+        ctx->triMatCount[3] = n;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->triMatStore + first, ids, count, hipMemcpyHostToDevice));
+    for (uint32_t k = 0; k < count; ++k) {
+        uint8_t& h = ctx->triMatHost[(size_t)first + k];
+        --ctx->triMatCount[h];
+        h = ids[k];
+        ++ctx->triMatCount[h];
+    }
+    census_classes(ctx);
+    ctx->dTriMat = ctx->triMatStore;
+    return RT_OK;
+}
+
+int rt_reset_triangle_materials(rt_context* ctx) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_reset_triangle_materials before rt_init"; return RT_ERR_STATE; }
+    if (int rc = sync_streams(ctx, false)) return rc;
+    ctx->dTriMat = nullptr;  // the null table: the launches of a context that never set one
+    ctx->triMatClasses = 0;
+    return RT_OK;
+}
+
 // a context-stream user of the current LBVH waits for its build on the side stream
 int wait_bvh(rt_context* ctx) {
     if (ctx->buildOnSide[ctx->bvhSet])
@@ -1078,6 +1148,7 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
         case RT_ARR_PT_Q3_DIRS:
         case RT_ARR_PT_Q4_ORIGINS:
         case RT_ARR_PT_Q4_DIRS: return (size_t)ctx->fr.ws.cap * 16;
+        case RT_ARR_TRI_MATERIALS: return (size_t)ctx->mesh.triCount;
         default: return 0;
     }
 }
@@ -1136,6 +1207,14 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
             float* o = (float*)dst;
             memcpy(o, ctx->fr.sunDir, 12);
             o[3] = ctx->fr.cosThetaMax;
+            return RT_OK;
+        }
+        case RT_ARR_TRI_MATERIALS: {  // what the kernels read; without a table the reference's, 3 everywhere
+            const size_t n = ctx->mesh.triCount;
+            if (bytes < n) { ctx->err = "destination too small"; return RT_ERR_ARG; }
+            if (!ctx->dTriMat) { memset(dst, 3, n); return RT_OK; }
+            if (int rc = sync_streams(ctx)) return rc;
+            HIP_TRY(ctx, hipMemcpy(dst, ctx->dTriMat, n, hipMemcpyDeviceToHost));
             return RT_OK;
         }
         default: ctx->err = "unknown array"; return RT_ERR_ARG;

@@ -304,6 +304,15 @@ struct rt_context {
     uint64_t builtEpoch = 0;
     bool dispValid[2] = {false, false};   // set k's build recorded a displacement (bvh[k].triDisp)
     bool dispTraced[2] = {false, false};  // ... and a path trace has applied it: later ones on that build do not
+    // per-triangle materials (rt_set_triangle_materials): null until the first set and after a reset,
+    // and then every launch is the one of a context without the feature.  triMatStore keeps the
+    // allocation across resets; the host copy gives the census of ids (triMatCount) and from it the
+    // kernel classes (rt_material_classes) without a device read
+    uint8_t* dTriMat = nullptr;         // [triCountPadded], 3 past what was set
+    uint8_t* triMatStore = nullptr;
+    std::vector<uint8_t> triMatHost;    // [triCount]
+    uint32_t triMatCount[256] = {};     // triangles per id
+    uint32_t triMatClasses = 0;         // RT_MAT_CLASS_* bits of the ids present
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
     // and the setters that change the stream drain it), and on a context without a post stream the

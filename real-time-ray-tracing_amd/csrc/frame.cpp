@@ -734,10 +734,18 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.ws.hitRec4 = p.ws.hitRec;  // one stream: queue 3's records are dead once queue 4 is traced
     p.ws.hitErr4 = p.ws.hitErr;
     p.ws.shade3 = fr.camShade3[qs];  // null: resume<3> unsplit ([tuning] resumeSplit = 0)
-    {  // material table (init.cu:215-251): only mirror / glass ids make steps 1-2 trace
+    {  // material table (init.cu:215-251): only mirror / glass ids make steps 1-2 trace, only id 4 is
+       // MICROFACET (rt_material_classes is the rule).  The override wins over the triangle table,
+       // which such a launch does not get; without either it is the reference table, 3 / 6: no class
         const int m = ctx->materialOverride;
-        p.ws.glossy = m >= 0 && (m == 1 || m == 5 || m >= 10);
-        p.ws.microfacet = m == 4;  // mat_type: only id 4 is MICROFACET, the reference table uses 3 / 6
+        uint32_t classes = ctx->dTriMat ? ctx->triMatClasses : 0u;
+        if (m >= 0) {
+            const uint8_t id = (uint8_t)(m > 255 ? 255 : m);  // every id >= 10 is of one class
+            (void)rt_material_classes(&id, 1, &classes);
+        }
+        p.triMat = m >= 0 ? nullptr : ctx->dTriMat;
+        p.ws.glossy = (classes & RT_MAT_CLASS_GLOSSY) != 0u;
+        p.ws.microfacet = (classes & RT_MAT_CLASS_MICROFACET) != 0u;
     }
     return qs;
 }
@@ -754,6 +762,9 @@ bool spec_matches(const PathTraceParams& a, uint64_t epochA, const PathTracePara
     // they read the LBVH set of the frame that launched them, the next frame reads the other: both
     // hold the same build (tests/test_gpu_bvh.py) exactly when no vertex update came between them
     if (epochA != epochB) return false;
+    // the triangle materials need no field here: rt_set_triangle_materials and its reset wait for the
+    // streams like every setter, and sync_streams drops what was traced ahead, so a launch that is
+    // still kept read the table (triMat's contents, not only its address) the next frame reads
     PathTraceParams x = a, y = b;
     for (PathTraceParams* q : {&x, &y}) {
         q->rayCounter = nullptr;  // the launches ahead count into specRayCounter

@@ -129,8 +129,9 @@ struct PtWorkspace {
     uint32_t traceBlocks;       // grid of the queue tracer of queue 3 (k_trace_queue)
     uint32_t trace3ShortBlocks = 0;  // its workgroups that run when queue 3 is short (0: all)
     uint32_t trace4Blocks;      // ... of queue 4 (a short queue: a few percent of queue 3)
-    int glossy;                 // materials can be glossy: steps 1-2 may trace (materialOverride)
-    int microfacet;             // materials can be the microfacet one (materialOverride 4): GGX compiled in
+    // rt_material_classes of materialOverride, or of the triangle table's census (fill_pt_params)
+    int glossy;                 // materials can be glossy: steps 1-2 may trace
+    int microfacet;             // materials can be the microfacet one (id 4): GGX compiled in
     int chain = 1;              // default materials: trace<3> .. resume<4> as one launch (k_pt_chain)
     uint32_t* itersOut = nullptr;  // optional [cap]: traversal iterations per queue entry (rt_trace_rays)
     unsigned long long* q3HostOut = nullptr;  // optional, pinned host memory: {queue 3's length, q3Tag},
@@ -202,6 +203,9 @@ struct PathTraceParams {
     // optional [triCountPadded][3] (geometry motion vectors, GeomDispParams::triDisp): set, the shade
     // kernel is followed by k_pt_geom_motion, which rewrites the motion of the pixels whose sample 0 hit
     const float4* triDisp;
+    // optional [triCountPadded] material id per triangle (SceneMaterial::materialsIdx, kernel.cuh:198-203;
+    // rt_set_triangle_materials); null: the reference table, 3 everywhere (update_material)
+    const uint8_t* triMat;
 };
 
 // TemporalSpatialDenoising + PostProcessing + CopyToOutput (denoise.hip)

@@ -82,8 +82,12 @@ struct PathVars {
 
 RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
     // values first, one store each: stores sunk behind a branch became a private array
-    const int id = P.materialOverride >= 0 ? P.materialOverride
-                   : (rs.objectIdx >= 0 && rs.objectIdx < (int)P.triCount) ? 3 : 6;  // SAFE_LOAD(.., 6)
+    // materialsIdx[objectIdx] (traverse.cuh:29-32): P.triMat, or 3 everywhere without a table
+    // (rt_set_triangle_materials; a uniform test, one byte load behind the hit record)
+    const bool inRange = rs.objectIdx >= 0 && rs.objectIdx < (int)P.triCount;
+    int tableId = 3;
+    if (P.triMat && inRange) tableId = (int)P.triMat[rs.objectIdx];
+    const int id = P.materialOverride >= 0 ? P.materialOverride : inRange ? tableId : 6;  // SAFE_LOAD(.., 6)
     const int type = (id >= 0 && id < 10) ? mat_type(id) : PERFECT_REFLECTION;
     rs.matId = rs.hit ? id : 99999;
     rs.matType = rs.hit ? type : MAT_SKY;
@@ -171,9 +175,9 @@ RT_DEV void tri_plane(const PathTraceParams& P, F2 uv, float lod, F3 normal, F3 
 }
 
 // DiffuseSurfaceInteraction (surfaceInteraction.cuh:36-310); random numbers rn[2*bounce] and
-// rn[2*bounce+1].  kMF: the material table can hold the microfacet material (id 4, only through
-// materialOverride); without it the GGX branch, whose live values set the kernels' register peak,
-// is not compiled in.
+// rn[2*bounce+1].  kMF: the material table can hold the microfacet material (id 4: materialOverride
+// or a triangle's entry, rt_material_classes); without it the GGX branch, whose live values set the
+// kernels' register peak, is not compiled in.
 template <bool kMF>
 RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     if (rs.hitLight || !rs.isDiffuse || rs.isOccluded) return;
@@ -1348,9 +1352,12 @@ dim3 shade_grid(const PathTraceParams* p, K kernel, int& cached) {
 
 template <bool kOneRound>
 void launch_shade_rounds(const PathTraceParams* p, hipStream_t stream) {
-    static int occ[3];
+    static int occ[4];
     const dim3 pb(256);
-    if (p->ws.glossy) {
+    if (p->ws.glossy && p->ws.microfacet) {  // a triangle table with both classes (rt_set_triangle_materials)
+        auto k = k_pt_shade0<true, true, kOneRound>;
+        hipLaunchKernelGGL(k, shade_grid(p, k, occ[3]), pb, 0, stream, *p);
+    } else if (p->ws.glossy) {
         auto k = k_pt_shade0<true, false, kOneRound>;
         hipLaunchKernelGGL(k, shade_grid(p, k, occ[0]), pb, 0, stream, *p);
     } else if (p->ws.microfacet) {
@@ -1455,9 +1462,9 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
                 (void)kernel(p->ws.microfacet ? k_pt_resume3_shade<true> : k_pt_resume3_shade<false>, pg, stream);
                 return forked ? hipSuccess : kernel(k_pt_resume3_lean, pg, stream);
             }
-            return kernel(p->ws.microfacet ? k_pt_resume<3, true, false>
-                          : p->ws.glossy   ? k_pt_resume<3, false, true>
-                                           : k_pt_resume<3, false, false>, pg, stream);
+            return kernel(p->ws.glossy       ? (p->ws.microfacet ? k_pt_resume<3, true, true> : k_pt_resume<3, false, true>)
+                          : p->ws.microfacet ? k_pt_resume<3, true, false>
+                                             : k_pt_resume<3, false, false>, pg, stream);
         });
         if (e == hipSuccess) e = stage([&] { return rtk_launch_trace_queue(p, 4, stream); });
         if (e == hipSuccess) e = stage([&] { return kernel(k_pt_resume<4, false, false>, pg, stream); });  // step 4 shades nothing

@@ -27,7 +27,7 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            SUN_PDF=22, SUN_CDF=23, SUN_DIR=24, HISTOGRAM=25, EXPOSURE=26, COLOR4=27, COLOR16=28, COLOR64=29,
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
-           BVH_ARENA=41)
+           BVH_ARENA=41, TRI_MATERIALS=42)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
@@ -165,7 +165,11 @@ SIGNATURES = {
     "rt_get_geometry_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_set_geometry_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_get_geometry_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_set_triangle_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rt_reset_triangle_materials": (C.c_int, [C.c_void_p]),
+    "rt_material_classes": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
+MAT_CLASS_GLOSSY, MAT_CLASS_MICROFACET = 1, 2  # RT_MAT_CLASS_*
 IMAGE_PPM_RGBA8, IMAGE_PFM_HDR = 0, 1
 DRAW_ASYNC = 1  # rt_draw_device flag
 BUF_SET1, BUF_SET2, BUF_SET3 = 0x100, 0x200, 0x300  # rt_bind_buffer: further G-buffer sets (frame pipelining)
@@ -391,6 +395,24 @@ class RayTracer:
     def geometry_motion(self, on: bool):
         self._check(self.lib.rt_set_geometry_motion(self.h, 1 if on else 0), "rt_set_geometry_motion")
 
+    # ---- per-triangle materials (rt_set_triangle_materials, include/rtx_amd.h)
+    def set_triangle_materials(self, ids: np.ndarray, first: int = 0):
+        """Material ids of triangles [first, first + len(ids)) from a contiguous 1-D uint8 array: 0..9
+        index the reference's material table, an id >= 10 is a mirror with that mask.  Takes effect
+        for every path trace enqueued after it; download("TRI_MATERIALS") returns the table."""
+        if not isinstance(ids, np.ndarray) or ids.dtype != np.uint8 or ids.ndim != 1:
+            raise ValueError("set_triangle_materials: ids must be a 1-D uint8 array")
+        if not ids.flags["C_CONTIGUOUS"]:
+            raise ValueError("set_triangle_materials: ids must be contiguous")
+        if not 0 <= int(first) <= 0xFFFFFFFF or len(ids) > 0xFFFFFFFF:
+            raise ValueError("set_triangle_materials: first and the triangle count must fit 32 bits")
+        self._check(self.lib.rt_set_triangle_materials(self.h, ids.ctypes.data, int(first), len(ids)),
+                    "rt_set_triangle_materials")
+
+    def reset_triangle_materials(self):
+        """Back to the reference's table, material 3 for every triangle."""
+        self._check(self.lib.rt_reset_triangle_materials(self.h), "rt_reset_triangle_materials")
+
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")
 
@@ -562,6 +584,17 @@ class RayTracer:
         out = np.empty(shape, dtype=dtype)
         self._check(self.lib.rt_get_buffer(self.h, BUF[name], out.ctypes.data, out.nbytes), "rt_get_buffer")
         return out
+
+
+def material_classes(ids) -> int:
+    """rt_material_classes: the MAT_CLASS_* bits of the kernel variants a table holding these ids
+    needs (mirror / glass ids: GLOSSY; id 4: MICROFACET).  Host only."""
+    a = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1)
+    c = C.c_uint32()
+    rc = load_library().rt_material_classes(a.ctypes.data if a.size else None, a.size, C.byref(c))
+    if rc != RT_OK:
+        raise RtError("rt_material_classes: %s" % ERRORS.get(rc, rc))
+    return c.value
 
 
 def _ptr(a):

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Cost of per-triangle materials on the GPU (rt_set_triangle_materials): pipelined
+1080p 4-spp frames on bench.py's terrain camera under six tables,
+
+  none        no table (the null pointer: today's launches)
+  all3        an explicit table of 3 everywhere
+  lambert     the Lambertian ids 3 / 7 / 8 / 9 scattered over the mesh
+  mirror1     1 % of the triangles mirror (id 5), the rest 3
+  mirror50    50 % mirror
+  mix8        the eight-way mix of the tests: 3 3 3 5 4 1 0 7 by a hash of the triangle index
+  none_again  no table again, at the end of each turn: the control, what two series of the same
+              launches differ by
+
+in ONE context whose table changes between the timed series (the setter drains the pipeline), the
+tables timed in turn --repeats times (--frames frames each, after --warmup frames under the new
+table), medians of ms per frame, so that a drift of the box's clocks falls on every table alike.
+One context per table, as tools/geom_probe.py times its modes, does not work for seven of them: the
+same launches ran 4.32 ms per frame in the context created first and 5.29 in the one created last
+(DESIGN.md §4.1.2), a context's place among the process's streams outweighing what is measured.  Whether the first three ran the same kernels is read from the launches, not from
+the times: rt_info.lastChain, the length of the queue-3 shading list (kept by the split plan only)
+and which kernel slots of marked frames are empty.  The mirror and mix rows carry no threshold: they
+are what a whole frame on the glossy plan costs today, the baseline for sorting surface pixels by
+material class.
+
+Writes profiles/materials.json.
+
+Usage: python tools/material_probe.py [--frames 100] [--repeats 5] [--out PATH]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "real-time-ray-tracing_amd")]
+
+TERRAIN_CAM = dict(pos=(8.0, 15.0, -6.0), yaw=0.0, pitch=-0.7)  # bench.py's
+MIX8 = (3, 3, 3, 5, 4, 1, 0, 7)
+EMPTY_SLOT_MS = 0.002  # two events with nothing between them
+
+
+def hashed(n, palette):
+    k = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761)) >> np.uint64(7)
+    return np.asarray(palette, np.uint8)[(k % np.uint64(len(palette))).astype(np.int64)]
+
+
+def tables(n):
+    """name -> uint8[n] (None: no table)."""
+    h = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) >> np.uint64(7)) % np.uint64(100)
+    return dict(none=None, none_again=None, all3=np.full(n, 3, np.uint8), lambert=hashed(n, (3, 7, 8, 9)),
+                mirror1=np.where(h < 1, 5, 3).astype(np.uint8), mirror50=np.where(h < 50, 5, 3).astype(np.uint8),
+                mix8=hashed(n, MIX8))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--marked", type=int, default=20, help="frames whose kernels are bracketed by events")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "materials.json"))
+    a = ap.parse_args()
+    import torch
+
+    import rtx
+    from rtx.frames import FramePipeline
+
+    w, h, spp = 1920, 1080, 4
+    dev = torch.device("cuda", 0)
+    prev = torch.cuda.current_stream(0)
+    names = ("none", "all3", "lambert", "mirror1", "mirror50", "mix8", "none_again")
+    rt = rtx.RayTracer(w, h, rtx.write_config(os.path.join(tempfile.mkdtemp(), "m.toml"), w, h, spp=spp)).init()
+    try:
+        rt.set_delta_time(16.667)
+        cam = rt.camera
+        cam.pos[:] = TERRAIN_CAM["pos"]
+        cam.yaw, cam.pitch = TERRAIN_CAM["yaw"], TERRAIN_CAM["pitch"]
+        rt.camera = cam
+        tabs = tables(int(rt.info().triCount))
+        fp = FramePipeline(rt, dev, pipelined=True)
+        state = dict(f=0)
+
+        def use(name):  # both calls are setters: they drain the pipeline first
+            if tabs[name] is None:
+                rt.reset_triangle_materials()
+            else:
+                rt.set_triangle_materials(tabs[name])
+                assert np.array_equal(rt.download("TRI_MATERIALS"), tabs[name])
+
+        def run(n):
+            for _ in range(n):
+                state["f"] += 1
+                fp.frame(state["f"])
+            fp.finish()
+
+        series = {name: [] for name in names}
+        for _ in range(a.repeats):
+            for name in names:
+                use(name)
+                run(a.warmup)
+                t0 = time.perf_counter()
+                run(a.frames)
+                series[name].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        rows = {}
+        for name in names:  # what was launched: marked frames, the plan, the shading list
+            use(name)
+            run(a.warmup)
+            rt.frame_marks_begin(a.marked)  # all 15: the path trace and the denoise / post kernels
+            run(a.marked)
+            ms, n = rt.frame_marks_read()
+            q = rt.download("PT_QUEUE", np.uint32)
+            ids = tabs[name]
+            census = {} if ids is None else {int(k): int(v) for k, v in zip(*np.unique(ids, return_counts=True))}
+            rows[name] = dict(
+                ms_per_frame=float(np.median(series[name])), series_ms=series[name],
+                classes=0 if ids is None else rtx.material_classes(ids), census=census,
+                last_chain=int(rt.info().lastChain), shading_list_entries=int(q[23]), queue3_entries=int(q[0]),
+                queue4_entries=int(q[1]), internal_errors=int(q[10]), marked_frames=n,
+                kernel_ms={k: round(v, 4) for k, v in ms.items()},
+                empty_slots=sorted(k for k, v in ms.items() if k in rt.PT_KERNELS and v < EMPTY_SLOT_MS))
+    finally:
+        rt.cleanup()
+        torch.cuda.set_stream(prev)
+
+    def plan(r):  # what tells the plans apart: the chain, a kept shading list, the slots that ran
+        return (r["last_chain"], r["shading_list_entries"] > 0, tuple(r["empty_slots"]))
+
+    for name in names:
+        rows[name]["same_kernels_as_none"] = plan(rows[name]) == plan(rows["none"])
+        rows[name]["cost_over_none_ms"] = rows[name]["ms_per_frame"] - rows["none"]["ms_per_frame"]
+    res = dict(device=torch.cuda.get_device_name(0),
+               config="%dx%d, %d spp, terrain camera %r, pipelined FramePipeline, LBVH rebuild every frame" % (w, h, spp, TERRAIN_CAM),
+               method="one context, the table changed between series; the tables timed in turn %d times, %d frames each "
+                      "after %d warm-up frames; ms_per_frame is the median of the series; kernel_ms from %d frames bracketed by events"
+                      % (a.repeats, a.frames, a.warmup, a.marked),
+               tables=rows)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
