@@ -26,7 +26,9 @@ extern "C" {
 #define RT_ERR_NO_DEVICE (-5)   /* no gfx950 device visible */
 #define RT_ERR_DEVICE (-6)      /* a kernel reported a failure (rt_last_error has the text): the LBVH's
                                    TLAS workgroup timed out waiting for a batch; the frames since the
-                                   last check may be wrong, the renderer re-armed itself.  Reported
+                                   last check may be wrong, the renderer re-armed itself; or
+                                   rt_set_mesh_device met indices past its vertex count and read
+                                   them as 0.  Reported
                                    once, by the call that finds it: rt_sync, rt_build_bvh, the draws
                                    and the reads (rt_get_buffer, rt_download, rt_get_ray_count,
                                    rt_save_image ...).  Setters (rt_set_*stream, rt_bind_buffer,
@@ -283,8 +285,8 @@ int rt_build_bvh(rt_context* ctx);
  * un-cleared buffer, angle-weighted, accumulated in triangle order (kernel.cu:228-257, 313-327), bit
  * for bit.  rt_download(RT_ARR_VERTICES / RT_ARR_NORMALS) return the updated arrays.
  *
- * Scope: the topology (indices, triangle and batch counts) is fixed.  The update takes effect for
- * every rt_build_bvh, explicit or inside a draw, enqueued after the call; frames already enqueued,
+ * Scope: the topology (indices, triangle and batch counts) stays as it is; rt_set_mesh below
+ * replaces it.  The update takes effect for every rt_build_bvh, explicit or inside a draw, enqueued after the call; frames already enqueued,
  * pipelined ones included, keep the geometry they were built from.  Nothing rebuilds by itself:
  * rt_trace_rays and rt_trace_primary still use the BVH of the last rt_build_bvh.
  *
@@ -319,7 +321,68 @@ int rt_build_bvh(rt_context* ctx);
 int rt_update_vertices(rt_context* ctx, const float* xyz, uint32_t first, uint32_t count);
 int rt_update_vertices_device(rt_context* ctx, const float* xyz_device, uint32_t first, uint32_t count,
                               void* ready_event);
-int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch); /* 0 after rt_init, +1 per update */
+int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch); /* 0 after rt_init, +1 per update / mesh set */
+
+/* Run-time mesh replacement (no reference counterpart): a live context gets a new indexed mesh,
+ * vertices and topology, stream-ordered like rt_update_vertices_device.
+ *
+ * Capacity: every mesh-sized buffer is allocated once, by rt_init, for [scene] maxTriangles /
+ * maxVertices (absent or 0: the init mesh's counts, and then every allocation is what it was without
+ * the keys).  maxTriangles <= 1024 * 1024 and its batch count ceil(maxTriangles / 1024) stays below
+ * 1024.  Unparsable or negative values: RT_ERR_IO from rt_create; a capacity below the init mesh or
+ * over the limits: RT_ERR_ARG from rt_init, before any device call.
+ *
+ * Effect: afterwards the vertices, the indices (padded to (n + 3) & ~3 triangles with index 0, as a
+ * meshFile's are), the vertex -> corner adjacency (rt_mesh_adjacency), the smooth normals and every
+ * LBVH build enqueued after the call, with every frame traced on those builds, equal those of a
+ * context whose rt_init had been given this mesh, bit for bit.  rt_get_info (triCount,
+ * triCountPadded, batchCount, vertexCount) and the mesh-level arrays (RT_ARR_VERTICES, INDICES,
+ * NORMALS, TRI_MATERIALS, ADJ_OFFSETS, CORNER_SLOTS) follow the new mesh at once; the BVH arrays
+ * (TRI_POS, TRI_NRM, AABBS, MORTON, REORDER, NODES, TLAS_*, BATCH_SCENE_AABBS, BVH_ARENA) keep the sizes
+ * and contents of the last build until the next one, and rt_array_bytes answers accordingly.
+ * Nothing rebuilds by itself, exactly as for vertex updates.
+ *
+ * Ordering: as for rt_update_vertices_device, for the index and adjacency arrays as for the
+ * vertices: the set runs after the last build enqueued on any of the renderer's streams, the next
+ * build waits for it, and the context stream follows the read of the caller's buffers.  Frames,
+ * prebuilds and ray queries already enqueued keep the geometry and the counts of the build they
+ * were issued on (each LBVH set carries its build's counts).  rt_set_mesh_device never synchronises
+ * the host and drains no stream; rt_set_mesh validates the indices, copies both arrays into staging
+ * buffers of the renderer (the caller's arrays are free on return) and takes the same device path.
+ *
+ * Interactions: the geometry epoch advances, so what a synchronous draw prepared ahead is
+ * discarded.  The per-triangle material table returns to the default (3 everywhere) as after
+ * rt_reset_triangle_materials, without a wait: launches already enqueued hold the old table, which is
+ * not written.  With geometry motion vectors on, the first build after the call records no
+ * displacement (the first-build rule).  Camera, frame number, exposure and history are untouched: a
+ * host that wants no temporal reuse across the cut sets the frame index to 1.  Multi-GPU: every rank
+ * calls with the same mesh.
+ *
+ * RT_ERR_ARG (checked in this order, NULL ctx / mesh first): a NULL or misaligned (4 B) array,
+ * triangle_count < 2 or above the capacity, vertex_count == 0 or above the capacity (the capacity
+ * checks need rt_init), and for rt_set_mesh an index >= vertex_count, with nothing changed.
+ * RT_ERR_STATE before rt_init.  Never RT_ERR_DEVICE from the call itself: rt_set_mesh_device cannot
+ * see its indices, so the kernel that copies them reads an index >= vertex_count as 0 (well defined,
+ * never an out-of-bounds access) and counts them; the next checking call (rt_sync, rt_build_bvh, a
+ * download) returns RT_ERR_DEVICE once, with the count in rt_last_error. */
+typedef struct rt_mesh {
+    const float* xyz;        /* vertex_count xyz triples */
+    uint32_t vertex_count;
+    const uint32_t* indices; /* 3 per triangle, each < vertex_count */
+    uint32_t triangle_count;
+    void* ready_event;       /* rt_set_mesh_device: hipEvent_t or NULL, as in rt_update_vertices_device */
+} rt_mesh;
+int rt_set_mesh(rt_context* ctx, const rt_mesh* host_mesh);
+int rt_set_mesh_device(rt_context* ctx, const rt_mesh* device_mesh);
+/* The vertex -> corner adjacency of an index array of padded_triangles triangles (host only, no
+ * device or context needed; what rt_init builds and the device kernels of rt_set_mesh reproduce):
+ * corner c (index c of the array) gets slot  adj_offsets[indices[c]] + #{c' < c : indices[c'] ==
+ * indices[c]},  adj_corners is the inverse (slot -> corner: the corners in a stable sort by vertex),
+ * adj_offsets[v] the first slot of vertex v and adj_offsets[vertex_count] = 3 * padded_triangles.
+ * adj_corners or corner_slots may be NULL.  RT_ERR_ARG: a NULL indices / adj_offsets, vertex_count
+ * == 0, or an index >= vertex_count. */
+int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32_t vertex_count,
+                      uint32_t* adj_offsets, uint32_t* adj_corners, uint32_t* corner_slots);
 
 /* Geometry motion vectors (no reference counterpart): off by default, and off nothing changes.  On,
  * the RT_BUF_MOTION G-buffer of a frame accounts for the vertices' displacement between the LBVH
@@ -352,7 +415,7 @@ int rt_get_geometry_motion(const rt_context* ctx, int* on);
 /* Per-triangle materials: SceneMaterial::materialsIdx (kernel.cuh:198-203, init.cu:261-269), the
  * material id the path tracer looks up at every hit (traverse.cuh:29-32).  ids[k] is the material of
  * triangle first + k, the objectIdx a hit reports; [first, first + count) lies within triCount
- * (rt_get_info), the topology being fixed as for rt_update_vertices.  Ids 0..9 index the reference's
+ * (rt_get_info) of the current mesh (rt_set_mesh resets the table).  Ids 0..9 index the reference's
  * material table (0, 2: emissive; 1: glass; 3, 6..9: Lambertian; 4: microfacet; 5: mirror); an id
  * >= 10 is the reference's out-of-range default, a mirror whose material mask is the id.  The mask
  * of RT_BUF_COLOR is the id of sample 0's triangle, which the denoiser's *_sigma_material weights
@@ -483,9 +546,15 @@ int rt_sync(rt_context* ctx);
 /* HIP-event timing on the context stream: runs `iters` back-to-back launches of a stage
  * (0 = BVH build, 1 = primary rays, 2 = path trace, 3 = full frame: BVH + path trace + denoise
  * + post, 4 = denoise + post, 5 = a whole-mesh vertex update with its smooth normals, fed the
- * current positions from a copy: arrays and epoch stay as they are) and returns the total
+ * current positions from a copy: arrays and epoch stay as they are, 6 = a whole-mesh set (rt_set_mesh_device)
+ * fed the current mesh from a copy, arrays and epoch likewise left as they are) and returns the total
  * milliseconds between the first launch and the end of the last. */
 int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms);
+
+/* Stage 6 split by HIP events between its launches: `iters` whole-mesh sets one after the other,
+ * parts_ms[0..2] = the summed milliseconds of the index ingest, of the adjacency kernels and of the
+ * whole-mesh normals update.  Measurement aid (tools/mesh_probe.py); waits for the streams. */
+int rt_time_mesh_set(rt_context* ctx, int iters, float* parts_ms);
 
 /* Test entry (no reference counterpart): the denoiser's packed-pair transcendentals (rtmath_pk.h)
  * beside their scalar rtmath.h forms, over a caller-owned device array x of n floats (element i
@@ -576,8 +645,11 @@ enum rt_array_name {
     RT_ARR_BVH_ARENA = 41,       /* the traversal's record arena as the device holds it (64-B records: B*1024 BLAS
                                     nodes, B TLAS nodes, triCountPadded triangle records); the
                                     NODES / TLAS_NODES / TRI_POS arrays are views of it in the reference layout */
-    RT_ARR_TRI_MATERIALS = 42    /* uint8[triCount] material id per triangle (rt_set_triangle_materials); all 3
+    RT_ARR_TRI_MATERIALS = 42,   /* uint8[triCount] material id per triangle (rt_set_triangle_materials); all 3
                                     before the first set and after a reset */
+    RT_ARR_ADJ_OFFSETS = 43,     /* uint32[nv + 1] first slot of each vertex in the vertex -> corner adjacency
+                                    (rt_mesh_adjacency) */
+    RT_ARR_CORNER_SLOTS = 44     /* uint32[3 * triCountPadded] each corner's slot in it */
 };
 int rt_download(const rt_context* ctx, int what, void* dst, size_t bytes);
 

@@ -7,6 +7,7 @@
 // report_status; checked by sync_streams and rt_build_bvh)
 constexpr int kStatusTlasTimeout = 0;       // the TLAS workgroup gave up waiting: the number of missing batches
 constexpr int kStatusTlasTimeoutBuild = 1;  // ... and the sequence number of the (last) build that did
+constexpr int kStatusMeshBadIndices = 2;    // rt_set_mesh_device: indices >= vertex_count, read as 0 (mesh.hip)
 
 struct BvhBuildParams {
     const float* vertices;     // [nv][3]
@@ -134,6 +135,31 @@ struct GeomDispParams {
     float4* triDisp;             // [triCountPadded][3] d1, d2, d3 in the order of the record's v1, v2, v3
     uint32_t triCountPadded;
 };
+
+// One mesh set (mesh.hip): the caller's indices copied, padded and range-checked into the context's
+// index array, and the vertex -> corner adjacency of the padded array (rt_mesh_adjacency is the
+// definition): a stable LSD radix sort of the corners by vertex id, 8 bits a pass.
+constexpr uint32_t kMeshSortThreads = 512;  // a sort workgroup; a tile is a multiple of it
+constexpr uint32_t kMeshTilesMax = 256;     // tiles (workgroups) of a pass: a digit's row of the [digit][tile] table is one workgroup's scan
+inline uint32_t mesh_tile_len(uint32_t corners) {
+    const uint32_t per = (corners + kMeshTilesMax - 1) / kMeshTilesMax;
+    return (per + kMeshSortThreads - 1) / kMeshSortThreads * kMeshSortThreads;
+}
+struct MeshSetParams {
+    const uint32_t* srcIndices;  // [triCount * 3] the caller's (device memory)
+    uint32_t triCount, triCountPadded, nverts;
+    uint32_t* indices;           // [triCountPadded * 3] out: src, an index >= nverts as 0, the padding 0
+    uint32_t* adjOffsets;        // [nverts + 1] out
+    uint32_t* adjCorner;         // [triCountPadded * 3] out: slot -> corner
+    uint32_t* cornerSlot;        // [triCountPadded * 3] out: corner -> slot
+    uint32_t* keys[2];           // sort scratch, [triCountPadded * 3] each
+    uint32_t* vals[2];
+    uint32_t* table;             // [256 * kMeshTilesMax + 256] digit counts per tile, scanned in place, and per digit
+    uint32_t* badCount;          // device word, zero between sets: the indices out of range
+    uint32_t* status;            // pinned host words (kStatusMeshBadIndices)
+};
+// afterIngest (optional) is recorded between the index ingest and the adjacency kernels
+extern "C" hipError_t rtk_launch_mesh_set(const MeshSetParams* p, hipStream_t stream, hipEvent_t afterIngest);
 
 extern "C" hipError_t rtk_launch_geometry_update(const GeomUpdateParams* p, hipStream_t stream);
 extern "C" hipError_t rtk_launch_geometry_displacement(const GeomDispParams* p, hipStream_t stream);

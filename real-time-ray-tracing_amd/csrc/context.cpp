@@ -280,6 +280,38 @@ int rt_scan_device(const float* in, float* out, float* tmp, int size, int block_
     return RT_OK;
 }
 
+// rt_init's vertex -> corner CSR (kernel.cu:313-327 walks it in triangle order) and its inverse; the
+// definition the device kernels of a mesh set reproduce (mesh.hip)
+int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32_t vertex_count, uint32_t* adj_offsets,
+                      uint32_t* adj_corners, uint32_t* corner_slots) {
+    if (!indices || !adj_offsets || vertex_count == 0) return RT_ERR_ARG;
+    const size_t n = (size_t)padded_triangles * 3;
+    for (size_t c = 0; c < n; ++c)
+        if (indices[c] >= vertex_count) return RT_ERR_ARG;
+    for (size_t v = 0; v <= vertex_count; ++v) adj_offsets[v] = 0;
+    for (size_t c = 0; c < n; ++c) adj_offsets[(size_t)indices[c] + 1]++;
+    for (size_t v = 0; v < vertex_count; ++v) adj_offsets[v + 1] += adj_offsets[v];
+    if (!adj_corners && !corner_slots) return RT_OK;
+    std::vector<uint32_t> fill(adj_offsets, adj_offsets + vertex_count);
+    for (size_t c = 0; c < n; ++c) {
+        const uint32_t slot = fill[indices[c]]++;
+        if (corner_slots) corner_slots[c] = slot;
+        if (adj_corners) adj_corners[slot] = (uint32_t)c;
+    }
+    return RT_OK;
+}
+
+// An LBVH set takes the current mesh's counts, and its arena the layout the build kernel's traversal
+// words assume for that batch count (traverse.h): TLAS nodes at B * 1024, triangle records behind
+// them.  The allocation is the capacity's, which holds the layout of every mesh within it.
+void arena_place(rt_context* ctx, BvhBufs& b) {
+    b.triCount = ctx->mesh.triCount;
+    b.triCountPadded = ctx->mesh.triCountPadded;
+    b.B = ctx->B;
+    b.tlasNodes = (char*)b.nodes + (size_t)b.B * 1024 * 64;
+    b.triPos = (float4*)((char*)b.nodes + ((size_t)b.B * 1024 + b.B) * 64);
+}
+
 int rt_create(int screen_width, int screen_height, const char* config_toml, rt_context** out) {
     if (!out) return RT_ERR_ARG;
     *out = nullptr;
@@ -314,6 +346,18 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
     ctx->minHeight = rttoml::find_or_int(doc, "optimziation", "minHeight", 480);
     ctx->chunkDim = rttoml::find_or_int(doc, "scene", "chunkDim", 1);
     ctx->meshFile = rttoml::find_or_string(doc, "scene", "meshFile", "");
+    for (const char* key : {"maxTriangles", "maxVertices"}) {  // rt_set_mesh's capacity: a count, 0 = the init mesh's
+        const rttoml::Value* v = rttoml::find(doc, "scene", key);
+        if (!v) continue;
+        char* end = nullptr;
+        const long long n = v->isArray || v->isString || v->raw.empty() ? -1 : strtoll(v->raw.c_str(), &end, 10);
+        if (n < 0 || n > 0xFFFFFFFFll || !end || *end != '\0') {
+            g_createError = std::string("config parse error: [scene] ") + key + " must be a count";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        (key[3] == 'T' ? ctx->maxTriangles : ctx->maxVertices) = (uint32_t)n;
+    }
     ctx->spp = rttoml::find_or_int(doc, "render", "spp", 1);
     ctx->bvhThreads = rttoml::find_or_int(doc, "render", "bvhThreads", 0);  // LBVH workgroup shape (A/B, tests)
     ctx->device = rttoml::find_or_int(doc, "render", "device", -1);
@@ -415,6 +459,16 @@ int rt_init(rt_context* ctx) {
     ctx->B = (N + 1023) / 1024;
     if (ctx->B >= 1024) { ctx->err = "batch count must stay below 1024 (init.cu:126)"; return RT_ERR_ARG; }
     ctx->nv = (uint32_t)(ctx->mesh.vertices.size() / 3);
+    // rt_set_mesh's capacity ([scene] maxTriangles / maxVertices; 0: this mesh), under the same limits
+    ctx->capTri = ctx->maxTriangles ? ctx->maxTriangles : N;
+    ctx->capNV = ctx->maxVertices ? ctx->maxVertices : ctx->nv;
+    if (ctx->capTri < N || ctx->capNV < ctx->nv) { ctx->err = "[scene] maxTriangles / maxVertices below the init mesh"; return RT_ERR_ARG; }
+    if (ctx->capTri > 1024u * 1024u || (ctx->capTri + 1023) / 1024 >= 1024) {
+        ctx->err = "[scene] maxTriangles out of range: at most 1048576 triangles in fewer than 1024 batches";
+        return RT_ERR_ARG;
+    }
+    ctx->capNP = (ctx->capTri + 3u) & ~3u;
+    ctx->capB = (ctx->capTri + 1023) / 1024;
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { ctx->err = "no HIP device visible"; return RT_ERR_NO_DEVICE; }
@@ -445,26 +499,29 @@ int rt_init(rt_context* ctx) {
 
     int rc;
 #define ALLOC(p, bytes) if ((rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    ALLOC(ctx->dVerts, (size_t)ctx->nv * 12);
-    ALLOC(ctx->dNormals, (size_t)ctx->nv * 12);
-    ALLOC(ctx->dIdx, (size_t)NP * 12);
-    // the record arena (traverse.h): BLAS nodes, TLAS nodes, triangle records, 64 B each
-    ALLOC(ctx->dNodes, arena_bytes(ctx->B, NP));
-    ctx->dTlasNodes = (char*)ctx->dNodes + (size_t)ctx->B * 1024 * 64;
-    ctx->dTriPos = (float4*)((char*)ctx->dNodes + ((size_t)ctx->B * 1024 + ctx->B) * 64);
-    ALLOC(ctx->dTriNrm, (size_t)NP * 48);
-    ALLOC(ctx->dAabbs, (size_t)NP * 24);
-    ALLOC(ctx->dBatchScene, (size_t)ctx->B * 24);
-    ALLOC(ctx->dMorton, (size_t)ctx->B * 4096);
-    ALLOC(ctx->dReorder, (size_t)ctx->B * 4096);
-    ALLOC(ctx->dTlasAabbs, (size_t)ctx->B * 24);
+    // every mesh-sized buffer by the capacity (rt_set_mesh), which without the config keys is this mesh
+    const size_t capNV = ctx->capNV, capNP = ctx->capNP, capB = ctx->capB;
+    ALLOC(ctx->dVerts, capNV * 12);
+    ALLOC(ctx->dNormals, capNV * 12);
+    ALLOC(ctx->dIdx, capNP * 12);
+    // the record arena (traverse.h): BLAS nodes, TLAS nodes, triangle records, 64 B each, laid out by the
+    // batch count of the mesh a build gathers (arena_place)
+    ALLOC(ctx->dNodes, arena_bytes(capB, capNP));
+    ALLOC(ctx->dTriNrm, capNP * 48);
+    ALLOC(ctx->dAabbs, capNP * 24);
+    ALLOC(ctx->dBatchScene, capB * 24);
+    ALLOC(ctx->dMorton, capB * 4096);
+    ALLOC(ctx->dReorder, capB * 4096);
+    ALLOC(ctx->dTlasAabbs, capB * 24);
     ALLOC(ctx->dTlasScene, 24);
     ALLOC(ctx->dTlasMorton, 4096);
     ALLOC(ctx->dTlasReorder, 4096);
     ALLOC(ctx->dCounter, 64);
-    ctx->bvh[0] = BvhBufs{ctx->dTriPos, ctx->dTriNrm, ctx->dAabbs, ctx->dBatchScene, ctx->dMorton, ctx->dReorder,
+    ctx->bvh[0] = BvhBufs{nullptr, ctx->dTriNrm, ctx->dAabbs, ctx->dBatchScene, ctx->dMorton, ctx->dReorder,
                           ctx->dNodes, ctx->dTlasAabbs, ctx->dTlasScene, ctx->dTlasMorton, ctx->dTlasReorder,
-                          ctx->dTlasNodes, ctx->dCounter};
+                          nullptr, ctx->dCounter};
+    arena_place(ctx, ctx->bvh[0]);
+    bvh_select(ctx, 0);
     ALLOC(ctx->dBlueNoise, 327680);
     const size_t P = (size_t)ctx->renderW * ctx->renderH;
     ALLOC(ctx->dHits, P * 16);
@@ -475,7 +532,7 @@ int rt_init(rt_context* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->dVerts, ctx->mesh.vertices.data(), (size_t)ctx->nv * 12, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->dIdx, ctx->mesh.indices.data(), (size_t)NP * 12, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemset(ctx->dCounter, 0, 64));
-    HIP_TRY(ctx, hipMemset(ctx->dNodes, 0, arena_bytes(ctx->B, NP)));
+    HIP_TRY(ctx, hipMemset(ctx->dNodes, 0, arena_bytes(capB, capNP)));
 
     std::string bn;
     if (!read_file(dataDir + "/bluenoise_4spp.bin", bn) || bn.size() != 327680) {
@@ -488,15 +545,12 @@ int rt_init(rt_context* ctx) {
     std::vector<uint32_t> slots((size_t)NP * 3);  // the CSR's inverse, corner -> slot (vertex updates)
     {
         std::vector<uint32_t> off(ctx->nv + 1, 0), corners((size_t)NP * 3);
-        for (size_t c = 0; c < (size_t)NP * 3; ++c) off[ctx->mesh.indices[c] + 1]++;
-        for (uint32_t v = 0; v < ctx->nv; ++v) off[v + 1] += off[v];
-        std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-        for (size_t c = 0; c < (size_t)NP * 3; ++c) {
-            slots[c] = fill[ctx->mesh.indices[c]]++;
-            corners[slots[c]] = (uint32_t)c;
+        if (rt_mesh_adjacency(ctx->mesh.indices.data(), NP, ctx->nv, off.data(), corners.data(), slots.data()) != RT_OK) {
+            ctx->err = "the mesh has an index past its vertices";
+            return RT_ERR_ARG;
         }
-        ALLOC(ctx->dAdjOff, off.size() * 4);
-        ALLOC(ctx->dAdjCorner, corners.size() * 4);
+        ALLOC(ctx->dAdjOff, (capNV + 1) * 4);
+        ALLOC(ctx->dAdjCorner, capNP * 12);
         HIP_TRY(ctx, hipMemcpy(ctx->dAdjOff, off.data(), off.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(ctx->dAdjCorner, corners.data(), corners.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, rtk_launch_smooth_normals(ctx->dVerts, ctx->dAdjOff, ctx->dAdjCorner, ctx->dIdx, ctx->nv,
@@ -506,8 +560,8 @@ int rt_init(rt_context* ctx) {
     if ((rc = rt_frame_init(ctx)) != RT_OK) return rc;
     // vertex updates (rt_update_vertices*, geometry.hip): their scratch and events exist from here on,
     // so that an update only enqueues work
-    if ((rc = dalloc(ctx, &ctx->dCornerSlot, slots.size() * 4)) != RT_OK) return rc;
-    if ((rc = dalloc(ctx, &ctx->dContrib, slots.size() * 12)) != RT_OK) return rc;
+    if ((rc = dalloc(ctx, &ctx->dCornerSlot, capNP * 12)) != RT_OK) return rc;
+    if ((rc = dalloc(ctx, &ctx->dContrib, capNP * 36)) != RT_OK) return rc;
     HIP_TRY(ctx, hipMemcpy(ctx->dCornerSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomSrc, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomDone, hipEventDisableTiming));
@@ -516,7 +570,20 @@ int rt_init(rt_context* ctx) {
     for (hipEvent_t* e : {&ctx->queryDone[0], &ctx->queryDone[1]})
         HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (ctx->geomMotion && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;  // [render] geometryMotion
+    // mesh sets (rt_set_mesh*, mesh.hip): the staging buffers of the host variants and the adjacency
+    // sort's scratch, behind every other buffer of rt_init, so that a set only enqueues work
+    if ((rc = dalloc(ctx, &ctx->dVertStage, capNV * 12)) != RT_OK) return rc;
+    if ((rc = dalloc(ctx, &ctx->dIdxStage, capNP * 12)) != RT_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = dalloc(ctx, &ctx->dSortKeys[k], capNP * 12)) != RT_OK) return rc;
+        if ((rc = dalloc(ctx, &ctx->dSortVals[k], capNP * 12)) != RT_OK) return rc;
+    }
+    if ((rc = dalloc(ctx, &ctx->dSortTable, ((size_t)256 * kMeshTilesMax + 256) * 4)) != RT_OK) return rc;
+    if ((rc = dalloc(ctx, &ctx->dMeshBad, 64)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipMemset(ctx->dMeshBad, 0, 64));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mesh.vertices = std::vector<float>();   // the device holds the mesh from here on
+    ctx->mesh.indices = std::vector<uint32_t>();
     ctx->inited = true;
     // CameraSetup (init.cu:433-435): a missing or short file leaves the default camera, and the
     // reference only prints its error, so this is not an rt_init failure either
@@ -656,6 +723,16 @@ int rt_build_bvh(rt_context* ctx) {
     }
     // the build gathers the vertices and normals of the last update, whichever stream that ran on
     if (ctx->geomDoneValid && stream != ctx->geomStream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->geomDone, 0));
+    {  // the set's first build on another mesh (rt_set_mesh): its counts and arena layout, over a cleared arena,
+       // so that what the build does not write reads zero as in a context initialised with this mesh
+        BvhBufs& b = ctx->bvh[ctx->bvhSet];
+        if (b.meshSerial != ctx->meshSerial) {
+            b.meshSerial = ctx->meshSerial;
+            arena_place(ctx, b);
+            bvh_select(ctx, ctx->bvhSet);
+            HIP_TRY(ctx, hipMemsetAsync(b.nodes, 0, arena_bytes(ctx->capB, ctx->capNP), stream));
+        }
+    }
     BvhBuildParams p;
     p.vertices = ctx->dVerts;
     p.normals = ctx->dNormals;
@@ -699,7 +776,7 @@ int rt_build_bvh(rt_context* ctx) {
             d.prevVerts = ctx->dPrevVerts;
             d.indices = ctx->dIdx;
             d.triDisp = ctx->bvh[k].triDisp;
-            d.triCountPadded = ctx->mesh.triCountPadded;
+            d.triCountPadded = ctx->bvh[k].triCountPadded;
             HIP_TRY(ctx, rtk_launch_geometry_displacement(&d, stream));
             ctx->dispValid[k] = true;
             ctx->dispTraced[k] = false;
@@ -721,8 +798,17 @@ int rt_build_bvh(rt_context* ctx) {
 // update is behind the last one and ahead of the next without an event, and beside the current
 // frame's trace chain), else the context stream.  `srcReady`: the source needs no ordering (the
 // renderer's staging copy); otherwise U waits for `ready`, or without one for the context stream.
+//
+// A mesh set (rt_set_mesh*) is the same update with `mesh` given: the index ingest and the adjacency
+// kernels (mesh.hip) run first on U, behind the same waits, since the builds' gather, the normals
+// kernels and the displacement kernel are the only readers of the index and adjacency arrays as they
+// are of the vertices; then the whole-mesh update with the new counts.
+struct MeshChange {
+    const uint32_t* indices;  // device memory, [triCount * 3]
+    uint32_t triCount, nverts;
+};
 static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t first, uint32_t count, hipEvent_t ready,
-                                 bool srcReady, bool bump) {
+                                 bool srcReady, bool bump, const MeshChange* mesh = nullptr) {
     hipStream_t u = ctx->postStream ? ctx->sideStream : ctx->stream;
     if (!srcReady) {
         if (ready) {
@@ -738,6 +824,41 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
         for (int k = 0; k < 2; ++k)
             if (ctx->sideBuilt[k]) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->buildDone[k], 0));
     if (ctx->geomDoneValid && ctx->geomStream != u) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->geomDone, 0));
+    hipEvent_t* marks = ctx->meshMarks;  // rt_time_mesh_set only
+    if (mesh) {
+        MeshSetParams m;
+        m.srcIndices = mesh->indices;
+        m.triCount = mesh->triCount;
+        m.triCountPadded = (mesh->triCount + 3u) & ~3u;
+        m.nverts = mesh->nverts;
+        m.indices = ctx->dIdx;
+        m.adjOffsets = ctx->dAdjOff;
+        m.adjCorner = ctx->dAdjCorner;
+        m.cornerSlot = ctx->dCornerSlot;
+        for (int k = 0; k < 2; ++k) {
+            m.keys[k] = ctx->dSortKeys[k];
+            m.vals[k] = ctx->dSortVals[k];
+        }
+        m.table = ctx->dSortTable;
+        m.badCount = ctx->dMeshBad;
+        m.status = ctx->status;
+        if (marks) HIP_TRY(ctx, hipEventRecord(marks[0], u));
+        HIP_TRY(ctx, rtk_launch_mesh_set(&m, u, marks ? marks[1] : nullptr));
+        if (marks) HIP_TRY(ctx, hipEventRecord(marks[2], u));
+        if (bump) {  // the context follows the new mesh from here; each LBVH set keeps its build's counts
+            ctx->mesh.triCount = m.triCount;
+            ctx->mesh.triCountPadded = m.triCountPadded;
+            ctx->mesh.cornerCount = m.triCount * 3;
+            ctx->B = (m.triCount + 1023) / 1024;
+            ctx->nv = m.nverts;
+            ++ctx->meshSerial;
+            // the material table back to the default, as rt_reset_triangle_materials leaves it but without
+            // a wait: launches in flight hold the old table by value, and the store is not written
+            ctx->dTriMat = nullptr;
+            ctx->triMatClasses = 0;
+            ctx->prevVertsValid = false;  // geometry motion: the next build is a first build
+        }
+    }
     GeomUpdateParams p;
     p.src = src;
     p.first = first;
@@ -752,9 +873,10 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
     p.triCountPadded = ctx->mesh.triCountPadded;
     // geometry motion vectors: the first update after a build keeps the positions that build gathered
     // (several updates before the next build count as one step); rt_time_stage(5) keeps nothing
-    const bool keep = bump && ctx->geomMotion && ctx->built && ctx->geomEpoch == ctx->builtEpoch;
+    const bool keep = bump && !mesh && ctx->geomMotion && ctx->built && ctx->geomEpoch == ctx->builtEpoch;
     p.prevVerts = keep ? ctx->dPrevVerts : nullptr;
     HIP_TRY(ctx, rtk_launch_geometry_update(&p, u));
+    if (mesh && marks) HIP_TRY(ctx, hipEventRecord(marks[3], u));
     if (keep) {
         ctx->prevVertsValid = true;
         ctx->prevVertsEpoch = ctx->geomEpoch;
@@ -787,9 +909,6 @@ int rt_update_vertices_device(rt_context* ctx, const float* xyz_device, uint32_t
 
 // the staging buffer, once no earlier update still reads it
 static int vertex_stage(rt_context* ctx) {
-    if (!ctx->dVertStage) {
-        if (int rc = dalloc(ctx, &ctx->dVertStage, (size_t)ctx->nv * 12)) return rc;
-    }
     if (ctx->geomDoneValid) HIP_TRY(ctx, hipEventSynchronize(ctx->geomDone));
     return RT_OK;
 }
@@ -808,17 +927,60 @@ int rt_get_geometry_epoch(const rt_context* ctx, uint64_t* epoch) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- mesh replacement
+//
+// Check order: NULL ctx / mesh, the arguments that need no context state, the init state, the capacity.
+static int check_mesh(rt_context* ctx, const rt_mesh* m, const char* who) {
+    if (!ctx || !m) return RT_ERR_ARG;
+    const char* bad = nullptr;
+    if (!m->xyz || !m->indices) bad = "xyz and indices must not be NULL";
+    else if ((((uintptr_t)m->xyz | (uintptr_t)m->indices) & 3u) != 0) bad = "xyz and indices must be 4-byte aligned";
+    else if (m->triangle_count < 2u) bad = "a mesh has at least 2 triangles";
+    else if (m->vertex_count == 0u) bad = "a mesh has at least 1 vertex";
+    if (bad) { ctx->err = std::string(who) + ": " + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = std::string(who) + " before rt_init"; return RT_ERR_STATE; }
+    if (m->triangle_count > ctx->capTri || m->vertex_count > ctx->capNV) {
+        ctx->err = std::string(who) + ": " + std::to_string(m->triangle_count) + " triangles / " +
+                   std::to_string(m->vertex_count) + " vertices exceed the capacity ([scene] maxTriangles " +
+                   std::to_string(ctx->capTri) + " / maxVertices " + std::to_string(ctx->capNV) + ")";
+        return RT_ERR_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_set_mesh_device(rt_context* ctx, const rt_mesh* mesh) {
+    if (int rc = check_mesh(ctx, mesh, "rt_set_mesh_device")) return rc;
+    const MeshChange mc{mesh->indices, mesh->triangle_count, mesh->vertex_count};
+    return enqueue_vertex_update(ctx, mesh->xyz, 0, mesh->vertex_count, (hipEvent_t)mesh->ready_event, false, true, &mc);
+}
+
+int rt_set_mesh(rt_context* ctx, const rt_mesh* mesh) {
+    if (int rc = check_mesh(ctx, mesh, "rt_set_mesh")) return rc;
+    const size_t ni = (size_t)mesh->triangle_count * 3;
+    for (size_t c = 0; c < ni; ++c)
+        if (mesh->indices[c] >= mesh->vertex_count) {
+            ctx->err = "rt_set_mesh: index " + std::to_string(mesh->indices[c]) + " of corner " + std::to_string(c) +
+                       " is not below vertex_count";
+            return RT_ERR_ARG;
+        }
+    if (int rc = vertex_stage(ctx)) return rc;  // the staging buffers, once no earlier update reads them
+    HIP_TRY(ctx, hipMemcpy(ctx->dVertStage, mesh->xyz, (size_t)mesh->vertex_count * 12, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dIdxStage, mesh->indices, ni * 4, hipMemcpyHostToDevice));
+    const MeshChange mc{ctx->dIdxStage, mesh->triangle_count, mesh->vertex_count};
+    return enqueue_vertex_update(ctx, ctx->dVertStage, 0, mesh->vertex_count, nullptr, true, true, &mc);
+}
+
 // ---------------------------------------------------------------- geometry motion vectors
 //
 // The previous-position array and the displacement records of the LBVH sets that exist (the second
 // set's are allocated with it, ensure_bvh_pair); once allocated they stay.
 int ensure_geometry_motion(rt_context* ctx) {
     if (!ctx->dPrevVerts) {
-        if (int rc = dalloc(ctx, &ctx->dPrevVerts, (size_t)ctx->nv * 12)) return rc;
+        if (int rc = dalloc(ctx, &ctx->dPrevVerts, (size_t)ctx->capNV * 12)) return rc;
     }
     for (BvhBufs& b : ctx->bvh)
         if (b.nodes && !b.triDisp) {
-            if (int rc = dalloc(ctx, &b.triDisp, (size_t)ctx->mesh.triCountPadded * 48)) return rc;
+            if (int rc = dalloc(ctx, &b.triDisp, (size_t)ctx->capNP * 48)) return rc;
         }
     return RT_OK;
 }
@@ -884,7 +1046,7 @@ int rt_set_triangle_materials(rt_context* ctx, const uint8_t* ids, uint32_t firs
     // the kernels in flight read the table, and camera rays traced ahead precede it (spec_matches)
     if (int rc = sync_streams(ctx, false)) return rc;
     if (!ctx->triMatStore) {
-        if (int rc = dalloc(ctx, &ctx->triMatStore, (size_t)ctx->mesh.triCountPadded)) return rc;
+        if (int rc = dalloc(ctx, &ctx->triMatStore, (size_t)ctx->capNP)) return rc;
     }
     if (!ctx->dTriMat) {  // the first set, or the first after a reset: the reference's table
         HIP_TRY(ctx, hipMemset(ctx->triMatStore, 3, (size_t)ctx->mesh.triCountPadded));
@@ -966,11 +1128,14 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
         const int rc2 = rt_set_post_stream(ctx, post);
         return rc != RT_OK ? rc : rc2;
     }
-    if (stage == 5) {  // the current positions again, from a copy: the arrays and the epoch stay as they are
+    const MeshChange same{ctx->dIdxStage, ctx->mesh.triCount, ctx->nv};  // stage 6
+    if (stage == 5 || stage == 6) {  // the current positions (and indices) again, from a copy: the arrays and the epoch stay as they are
         int rc = sync_streams(ctx, false);
         if (rc == RT_OK) rc = vertex_stage(ctx);
         if (rc != RT_OK) return rc;
         HIP_TRY(ctx, hipMemcpy(ctx->dVertStage, ctx->dVerts, (size_t)ctx->nv * 12, hipMemcpyDeviceToDevice));
+        if (stage == 6)
+            HIP_TRY(ctx, hipMemcpy(ctx->dIdxStage, ctx->dIdx, (size_t)ctx->mesh.triCount * 12, hipMemcpyDeviceToDevice));
         HIP_TRY(ctx, hipDeviceSynchronize());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -978,6 +1143,7 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
         int rc = RT_OK;
         if (stage == 0) rc = rt_build_bvh(ctx);
         else if (stage == 5) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false);
+        else if (stage == 6) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false, &same);
         else if (stage == 1) rc = rt_trace_primary(ctx, 1 + i, 0);
         else if (stage == 2) rc = rt_path_trace(ctx, 1 + i, 0);
         else if (stage == 3) {
@@ -992,6 +1158,39 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
     HIP_TRY(ctx, hipEventElapsedTime(total_ms, ctx->ev0, ctx->ev1));
     return RT_OK;
+}
+
+// Stage 6 split by HIP events between its launches: parts_ms = the sums over `iters` sets of the index
+// ingest, the adjacency kernels and the whole-mesh normals update
+int rt_time_mesh_set(rt_context* ctx, int iters, float* parts_ms) {
+    if (!ctx || !parts_ms || iters < 1) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_time_mesh_set before rt_init"; return RT_ERR_STATE; }
+    if (ctx->postStream) {  // timed serially on the context stream, as rt_time_stage
+        void* post = ctx->postStream;
+        int rc = rt_set_post_stream(ctx, nullptr);
+        if (rc == RT_OK) rc = rt_time_mesh_set(ctx, iters, parts_ms);
+        const int rc2 = rt_set_post_stream(ctx, post);
+        return rc != RT_OK ? rc : rc2;
+    }
+    hipEvent_t marks[4] = {};
+    int rc = RT_OK;
+    for (hipEvent_t& e : marks)
+        if (hipEventCreate(&e) != hipSuccess) { rc = RT_ERR_HIP; ctx->err = "hipEventCreate failed"; }
+    parts_ms[0] = parts_ms[1] = parts_ms[2] = 0.0f;
+    ctx->meshMarks = marks;
+    for (int i = 0; i < iters && rc == RT_OK; ++i) {
+        float one = 0.0f;
+        if ((rc = rt_time_stage(ctx, 6, 1, &one)) != RT_OK) break;  // ends with the stream idle
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, marks[k], marks[k + 1]) != hipSuccess) { rc = RT_ERR_HIP; ctx->err = "HIP event timing failed"; }
+            parts_ms[k] += ms;
+        }
+    }
+    ctx->meshMarks = nullptr;
+    for (hipEvent_t e : marks)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
 }
 
 // per-kernel HIP-event split of `iters` path traces: serial ones (stage 2 of rt_time_stage) or,
@@ -1104,11 +1303,16 @@ int rt_frame_marks_read(rt_context* ctx, float* kernel_ms, int n, int* frames_re
 
 size_t rt_array_bytes(const rt_context* ctx, int what) {
     if (!ctx) return 0;
-    const size_t NP = ctx->mesh.triCountPadded, B = ctx->B, P = (size_t)ctx->renderW * ctx->renderH;
+    // the BVH arrays have the sizes of the current set's last build (before one, the init mesh's), the
+    // mesh-level arrays the current mesh's (rt_set_mesh)
+    const BvhBufs& set = ctx->bvh[ctx->bvhSet];
+    const size_t NP = set.triCountPadded, B = set.B, P = (size_t)ctx->renderW * ctx->renderH;
     switch (what) {
         case RT_ARR_VERTICES: return (size_t)ctx->nv * 12;
-        case RT_ARR_INDICES: return NP * 12;
+        case RT_ARR_INDICES: return (size_t)ctx->mesh.triCountPadded * 12;
         case RT_ARR_NORMALS: return (size_t)ctx->nv * 12;
+        case RT_ARR_ADJ_OFFSETS: return ((size_t)ctx->nv + 1) * 4;
+        case RT_ARR_CORNER_SLOTS: return (size_t)ctx->mesh.triCountPadded * 12;
         case RT_ARR_TRI_POS: return NP * 48;
         case RT_ARR_TRI_NRM: return NP * 48;
         case RT_ARR_AABBS: return NP * 24;
@@ -1162,6 +1366,8 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_VERTICES: src = ctx->dVerts; break;
         case RT_ARR_INDICES: src = ctx->dIdx; break;
         case RT_ARR_NORMALS: src = ctx->dNormals; break;
+        case RT_ARR_ADJ_OFFSETS: src = ctx->dAdjOff; break;
+        case RT_ARR_CORNER_SLOTS: src = ctx->dCornerSlot; break;
         case RT_ARR_TRI_POS: src = ctx->dTriPos; break;
         case RT_ARR_TRI_NRM: src = ctx->dTriNrm; break;
         case RT_ARR_AABBS: src = ctx->dAabbs; break;
@@ -1223,7 +1429,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
     if (bytes < need) { ctx->err = "destination too small"; return RT_ERR_ARG; }
     if (int rc = sync_streams(ctx)) return rc;
     if (what == RT_ARR_TRI_POS) {  // the arena's 64-B triangle records -> the reference's [N][3] float4
-        HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, ctx->mesh.triCountPadded, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, ctx->bvh[ctx->bvhSet].triCountPadded, hipMemcpyDeviceToHost));
         return RT_OK;
     }
     HIP_TRY(ctx, hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));

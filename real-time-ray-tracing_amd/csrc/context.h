@@ -41,6 +41,10 @@ struct BvhBufs {
     void* tlasNodes = nullptr;
     uint32_t* counter = nullptr;
     float4* triDisp = nullptr;  // geometry motion vectors: the records' corner displacements (allocated on enable)
+    // the mesh of the set's last build (rt_set_mesh): what every reader of the set goes by, the
+    // context's counts being the current mesh's.  tlasNodes and triPos follow B (rt_build_bvh).
+    uint32_t triCount = 0, triCountPadded = 0, B = 0;
+    uint64_t meshSerial = 0;    // rt_context::meshSerial at that build
 };
 
 // G-buffer sets in flight with frame pipelining: with four, frame f+4's camera rays wait for the
@@ -201,6 +205,7 @@ struct rt_context {
     std::vector<std::string> inputTextureFileNames;
     bool loadCameraAtInit = false;
     int chunkDim = 1;
+    uint32_t maxTriangles = 0, maxVertices = 0;  // [scene] maxTriangles / maxVertices: rt_set_mesh's capacity (0: the init mesh)
     std::string meshFile;  // [scene] meshFile: meshProcessor .bin instead of the procedural scene
     int spp = 1;
     int bvhThreads = 0;  // LBVH workgroup shape: 0 = by batch count, 512 or 1024 ([render] bvhThreads)
@@ -251,8 +256,11 @@ struct rt_context {
     InputState input;
 
     // ---- scene
-    rtscene::SceneMesh mesh;
+    rtscene::SceneMesh mesh;  // the current mesh's counts (rt_set_mesh); the host arrays are rt_init's only
     uint32_t B = 0, nv = 0;
+    // what every mesh-sized buffer is allocated for ([scene] maxTriangles / maxVertices)
+    uint32_t capTri = 0, capNP = 0, capB = 0, capNV = 0;
+    uint64_t meshSerial = 0;  // +1 per rt_set_mesh: a set's first build on a new mesh clears its arena
 
     // ---- device
     int cuCount = 0;                   // the device's CUs (LBVH workgroup shape)
@@ -291,7 +299,14 @@ struct rt_context {
     bool sideBuilt[2] = {false, false}; // buildDone[k] has been recorded (a build of set k on the side stream)
     uint32_t* dCornerSlot = nullptr;    // corner -> slot in the vertex -> corner CSR (dAdjCorner's inverse)
     float* dContrib = nullptr;          // the corners' normal contributions in CSR order (geometry.hip)
-    float* dVertStage = nullptr;        // rt_update_vertices' host positions / rt_time_stage(5)'s copy
+    float* dVertStage = nullptr;        // rt_update_vertices' / rt_set_mesh's host positions, rt_time_stage(5, 6)'s copy
+    // rt_set_mesh* (mesh.hip): the index staging and the adjacency sort's scratch, allocated by rt_init
+    uint32_t* dIdxStage = nullptr;
+    uint32_t* dSortKeys[2] = {};
+    uint32_t* dSortVals[2] = {};
+    uint32_t* dSortTable = nullptr;
+    uint32_t* dMeshBad = nullptr;
+    hipEvent_t* meshMarks = nullptr;    // set only inside rt_time_mesh_set: {start, after ingest, after adjacency, end}
     // geometry motion vectors (rt_set_geometry_motion): the motion buffer of the first
     // path trace on a build follows the vertices' displacement since the previous build.  dPrevVerts
     // is written by the first update after a build (k_geom_vertices) and read by the displacement
@@ -404,6 +419,7 @@ bool strip_local_denoise(const rt_context* ctx, uint32_t& a, uint32_t& b);  // f
 extern "C" int copy_rgba_out(rt_context* ctx, void* dst);  // frame.cpp: the last frame's RGBA8 to host memory
 extern "C" size_t rt_alloc_bytes(const rt_context* ctx, int name);  // frame.cpp: allocated size of a render buffer
 extern "C" void bvh_select(rt_context* ctx, int k);  // context.cpp: point the dTriPos.. views at bvh[k]
+extern "C" void arena_place(rt_context* ctx, BvhBufs& b);  // context.cpp: set b takes the current mesh's counts and arena layout
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
 extern "C" int ensure_geometry_motion(rt_context* ctx);  // context.cpp: dPrevVerts and the existing LBVH sets' triDisp
 std::string rt_data_dir();

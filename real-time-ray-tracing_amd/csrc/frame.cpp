@@ -372,6 +372,12 @@ void poll_q3(rt_context* ctx) {
 // and the launch counters of both LBVH sets are re-armed (a batch that never published left its
 // set's counter one short).  Called after the streams are idle (sync_streams) or before a build.
 int check_device_status(rt_context* ctx) {
+    // rt_set_mesh_device: indices past the vertex count, which the ingest kernel read as 0 (mesh.hip)
+    if (const uint32_t badIdx = __atomic_load_n(&ctx->status[kStatusMeshBadIndices], __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(&ctx->status[kStatusMeshBadIndices], 0u, __ATOMIC_RELEASE);
+        ctx->err = "rt_set_mesh_device: " + std::to_string(badIdx) + " index(es) not below vertex_count were read as 0";
+        return RT_ERR_DEVICE;
+    }
     const uint32_t missing = __atomic_load_n(&ctx->status[kStatusTlasTimeout], __ATOMIC_ACQUIRE);
     if (!missing) return RT_OK;
     const uint32_t build = __atomic_load_n(&ctx->status[kStatusTlasTimeoutBuild], __ATOMIC_ACQUIRE);
@@ -688,7 +694,7 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.spp = (uint32_t)ctx->spp;
     p.invSpp = (ctx->spp & (ctx->spp - 1)) == 0 ? 1.0f / (float)ctx->spp : 0.0f;  // exact for a power of two
     p.materialOverride = ctx->materialOverride;
-    p.triCount = ctx->mesh.triCount;
+    p.triCount = ctx->bvh[ctx->bvhSet].triCount;  // of the build the frame is traced on (rt_set_mesh)
     p.bluenoise = ctx->dBlueNoise;
     p.triPos = ctx->dTriPos;
     p.triNrm = ctx->dTriNrm;
@@ -1362,13 +1368,13 @@ int ensure_bvh_pair(rt_context* ctx) {
     int rc;
 #define ALLOC(p, bytes) if (!(p) && (rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
     {
-        const size_t NP = ctx->mesh.triCountPadded, B = ctx->B;
+        const size_t NP = ctx->capNP, B = ctx->capB;  // by the capacity, as in rt_init
         BvhBufs& b = ctx->bvh[1];
         if (!b.nodes) {  // the record arena (traverse.h), as in rt_init
             ALLOC(b.nodes, arena_bytes(B, NP));
             HIP_TRY(ctx, hipMemset(b.nodes, 0, arena_bytes(B, NP)));
-            b.tlasNodes = (char*)b.nodes + B * 1024 * 64;
-            b.triPos = (float4*)((char*)b.nodes + (B * 1024 + B) * 64);
+            arena_place(ctx, b);
+            b.meshSerial = ctx->meshSerial;
         }
         ALLOC(b.triNrm, NP * 48);
         if (ctx->geomMotion) ALLOC(b.triDisp, NP * 48);  // else with rt_set_geometry_motion (ensure_geometry_motion)

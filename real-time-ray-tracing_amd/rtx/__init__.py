@@ -27,7 +27,7 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            SUN_PDF=22, SUN_CDF=23, SUN_DIR=24, HISTOGRAM=25, EXPOSURE=26, COLOR4=27, COLOR16=28, COLOR64=29,
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
-           BVH_ARENA=41, TRI_MATERIALS=42)
+           BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
@@ -102,6 +102,12 @@ class RayQuery(C.Structure):
                 ("ready_event", C.c_void_p), ("done_event", C.c_void_p)]
 
 
+class Mesh(C.Structure):
+    """rt_mesh: an indexed mesh for rt_set_mesh / rt_set_mesh_device."""
+    _fields_ = [("xyz", C.c_void_p), ("vertex_count", C.c_uint32), ("indices", C.c_void_p),
+                ("triangle_count", C.c_uint32), ("ready_event", C.c_void_p)]
+
+
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
 
@@ -163,6 +169,10 @@ SIGNATURES = {
     "rt_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rt_get_geometry_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_set_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh)]),
+    "rt_set_mesh_device": (C.c_int, [C.c_void_p, C.POINTER(Mesh)]),
+    "rt_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_time_mesh_set": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "rt_set_geometry_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_get_geometry_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_set_triangle_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
@@ -210,14 +220,17 @@ class RtError(RuntimeError):
 def write_config(path: str, width: int, height: int, dynamic: bool = False, chunk_dim: int = 1, spp: int = 1,
                  extra: str = "", max_size=(3840, 2160), camera_file: str | None = None, min_size=(640, 480),
                  target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None,
-                 geometry_motion: bool | None = None) -> str:
+                 geometry_motion: bool | None = None, max_triangles: int | None = None,
+                 max_vertices: int | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
     RTX_TUNING environment variable ("key=value,key=value", e.g. "chain=off,tracePerCu=2") fills
     it: the A/B tools (tools/ab.sh) set it per variant.  The library itself reads no environment.
     `geometry_motion`: [render] geometryMotion, the initial state of rt_set_geometry_motion (None:
-    the key is not written, the default is off)."""
+    the key is not written, the default is off).
+    `max_triangles` / `max_vertices`: [scene] maxTriangles / maxVertices, the capacity of set_mesh
+    (None: the keys are not written, the capacity is the init mesh)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -231,6 +244,10 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
         f.write("[scene]\nchunkDim = %d\n" % chunk_dim)
         if mesh_file:  # a meshProcessor .bin instead of the procedural terrain (init.cu:28-50)
             f.write('meshFile = "%s"\n' % mesh_file)
+        if max_triangles is not None:
+            f.write("maxTriangles = %s\n" % max_triangles)
+        if max_vertices is not None:
+            f.write("maxVertices = %s\n" % max_vertices)
         f.write("\n[render]\nspp = %d\n" % spp)
         if geometry_motion is not None:
             f.write("geometryMotion = %s\n" % ("true" if geometry_motion else "false"))
@@ -377,9 +394,40 @@ class RayTracer:
         self._check(self.lib.rt_update_vertices_device(self.h, ptr, int(first), int(count), ready_event),
                     "rt_update_vertices_device")
 
+    # ---- mesh replacement (rt_set_mesh*, include/rtx_amd.h)
+    def set_mesh(self, vertices: np.ndarray, indices: np.ndarray):
+        """A new indexed mesh from host arrays: (nv, 3) float32 positions and (ntri, 3) uint32 indices,
+        C-contiguous, within the capacity ([scene] maxTriangles / maxVertices).  The smooth normals
+        and every later build_bvh / draw follow; info() and the mesh-level downloads at once."""
+        if not isinstance(vertices, np.ndarray) or vertices.dtype != np.float32 or vertices.ndim != 2 or vertices.shape[1] != 3:
+            raise ValueError("set_mesh: vertices must be an (n, 3) float32 array")
+        if not isinstance(indices, np.ndarray) or indices.dtype != np.uint32 or indices.ndim != 2 or indices.shape[1] != 3:
+            raise ValueError("set_mesh: indices must be an (n, 3) uint32 array")
+        if not vertices.flags["C_CONTIGUOUS"] or not indices.flags["C_CONTIGUOUS"]:
+            raise ValueError("set_mesh: the arrays must be C-contiguous")
+        if len(vertices) > 0xFFFFFFFF or len(indices) > 0xFFFFFFFF:
+            raise ValueError("set_mesh: the counts must fit 32 bits")
+        m = Mesh(vertices.ctypes.data, len(vertices), indices.ctypes.data, len(indices), None)
+        self._check(self.lib.rt_set_mesh(self.h, C.byref(m)), "rt_set_mesh")
+
+    def set_mesh_device(self, xyz_ptr: int, nv: int, idx_ptr: int, ntri: int, ready_event: int | None = None):
+        """The same from device memory (nv xyz float32 triples at xyz_ptr, ntri uint32 index triples
+        at idx_ptr), asynchronous; ready_event as in update_vertices_device."""
+        if not 0 <= int(nv) <= 0xFFFFFFFF or not 0 <= int(ntri) <= 0xFFFFFFFF:
+            raise ValueError("set_mesh_device: nv and ntri must fit 32 bits")
+        m = Mesh(xyz_ptr, int(nv), idx_ptr, int(ntri), ready_event)
+        self._check(self.lib.rt_set_mesh_device(self.h, C.byref(m)), "rt_set_mesh_device")
+
+    def time_mesh_set(self, iters: int = 1):
+        """(ingest, adjacency, normals) milliseconds summed over `iters` whole-mesh sets of the
+        current mesh (rt_time_mesh_set)."""
+        ms = (C.c_float * 3)()
+        self._check(self.lib.rt_time_mesh_set(self.h, iters, ms), "rt_time_mesh_set")
+        return tuple(float(v) for v in ms)
+
     @property
     def geometry_epoch(self) -> int:
-        """0 after init, +1 per vertex update."""
+        """0 after init, +1 per vertex update or mesh set."""
         v = C.c_uint64()
         self._check(self.lib.rt_get_geometry_epoch(self.h, C.byref(v)), "rt_get_geometry_epoch")
         return v.value
@@ -595,6 +643,22 @@ def material_classes(ids) -> int:
     if rc != RT_OK:
         raise RtError("rt_material_classes: %s" % ERRORS.get(rc, rc))
     return c.value
+
+
+def mesh_adjacency(indices_padded, nv: int):
+    """rt_mesh_adjacency: (adj_offsets[nv + 1], adj_corners[3 NP], corner_slots[3 NP]) of a padded
+    index array, the vertex -> corner adjacency rt_init builds and set_mesh reproduces.  Host only."""
+    a = np.ascontiguousarray(indices_padded, dtype=np.uint32).reshape(-1)
+    if a.size % 3:
+        raise ValueError("mesh_adjacency: three indices per triangle")
+    off = np.empty(int(nv) + 1, np.uint32)
+    corners = np.empty(a.size, np.uint32)
+    slots = np.empty(a.size, np.uint32)
+    rc = load_library().rt_mesh_adjacency(a.ctypes.data, a.size // 3, int(nv), off.ctypes.data, corners.ctypes.data,
+                                          slots.ctypes.data)
+    if rc != RT_OK:
+        raise RtError("rt_mesh_adjacency: %s" % ERRORS.get(rc, rc))
+    return off, corners, slots
 
 
 def _ptr(a):
