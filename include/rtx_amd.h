@@ -441,6 +441,49 @@ int rt_reset_triangle_materials(rt_context* ctx);
  * needed.  RT_ERR_ARG: classes NULL, or ids NULL with n > 0. */
 int rt_material_classes(const uint8_t* ids, size_t n, uint32_t* classes);
 
+/* The same set from device memory, stream-ordered: the counterpart of rt_update_vertices_device and
+ * rt_set_mesh_device for the material table.  The host is never synchronised and no stream is
+ * drained.  ids is read after ready_event (a hipEvent_t), or after everything enqueued on the
+ * context stream so far when it is NULL; work enqueued on the context stream after the call follows
+ * that read.  The new table (the previous one, or 3 everywhere after rt_set_mesh* or a reset, with
+ * [first, first + count) replaced) holds for every rt_path_trace enqueued after the call, explicit
+ * or inside a draw; path traces enqueued before it, pipelined frames in flight and what a
+ * synchronous draw traced ahead included, keep the table they were launched with, and the next draw
+ * traces again what was traced ahead.  The intended streaming sequence is rt_set_mesh_device,
+ * rt_set_triangle_materials_device, rt_build_bvh, a draw, with no wait in it.
+ *
+ * classes: the host cannot see the ids, and the path tracer picks its kernel variants from their
+ * classes, so the caller declares them: RT_MAT_CLASS_* bits (rt_material_classes is the rule) that
+ * bound the classes of EVERY id the table holds after the update, the carried-over ones included.
+ * Later frames launch exactly the kernels of the declared bits.  Declaring too much costs speed only
+ * and changes no pixel.  Declaring too little is a caller error handled like an index past the
+ * vertex count in rt_set_mesh_device: the kernel stores id 3 in place of every id of an undeclared
+ * class, carried-over ones too, and counts them; the next checking call (rt_sync, rt_build_bvh, a
+ * draw, a download) returns RT_ERR_DEVICE once, with the count in rt_last_error.
+ *
+ * Afterwards the host setter's copy is stale: rt_set_triangle_materials reads the table back before
+ * it applies its range (it waits for the streams anyway), and its census is exact again.
+ * RT_ARR_TRI_MATERIALS returns the current table and RT_ARR_TRI_MATERIAL_CENSUS its triangle count
+ * per id.  Every rank of a multi-GPU run calls with the same data.  The first call of a context
+ * allocates the table buffers (four of one byte per triangle of the capacity) and may block in the
+ * allocator; later calls only enqueue work.
+ * Checked in this order: RT_ERR_ARG for NULL ctx or u, NULL ids, count == 0, unknown bits in classes;
+ * RT_ERR_STATE before rt_init; RT_ERR_ARG for first + count > triCount of the current mesh;
+ * RT_ERR_HIP for a failed allocation or launch.  On an error nothing is changed.  Never
+ * RT_ERR_DEVICE from the call itself. */
+#define RT_MAT_CLASS_ALL (RT_MAT_CLASS_GLOSSY | RT_MAT_CLASS_MICROFACET)
+typedef struct rt_material_update {
+    const uint8_t* ids;    /* device memory, count bytes, no alignment demanded */
+    uint32_t first, count; /* triangles [first, first + count) of the current mesh */
+    uint32_t classes;      /* RT_MAT_CLASS_* bits: the caller's bound on the WHOLE table after this update */
+    void* ready_event;     /* hipEvent_t or NULL, as in rt_update_vertices_device */
+} rt_material_update;
+int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* u);
+/* The class of one id (its low 8 bits) as the device kernel of rt_set_triangle_materials_device
+ * computes it: the kernel's own statement of the rule, compiled for the host, so that a test can pin
+ * it to rt_material_classes.  No context needed. */
+uint32_t rt_material_class_rule(uint32_t id);
+
 /* BASELINE config 2: GenerateRay + RaySceneIntersect for every render pixel with the
  * blue-noise sample of frame_num (pathtrace.cuh:116-130), enqueued asynchronously.
  * with_detail != 0 also stores normals / shading normals / traversal counters. */
@@ -649,7 +692,10 @@ enum rt_array_name {
                                     before the first set and after a reset */
     RT_ARR_ADJ_OFFSETS = 43,     /* uint32[nv + 1] first slot of each vertex in the vertex -> corner adjacency
                                     (rt_mesh_adjacency) */
-    RT_ARR_CORNER_SLOTS = 44     /* uint32[3 * triCountPadded] each corner's slot in it */
+    RT_ARR_CORNER_SLOTS = 44,    /* uint32[3 * triCountPadded] each corner's slot in it */
+    RT_ARR_TRI_MATERIAL_CENSUS = 45 /* uint32[256] triangles per material id of the current table over [0, triCount):
+                                    the device census after rt_set_triangle_materials_device, the host's after
+                                    rt_set_triangle_materials, triCount at id 3 without a table */
 };
 int rt_download(const rt_context* ctx, int what, void* dst, size_t bytes);
 

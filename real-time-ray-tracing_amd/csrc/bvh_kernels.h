@@ -8,6 +8,7 @@
 constexpr int kStatusTlasTimeout = 0;       // the TLAS workgroup gave up waiting: the number of missing batches
 constexpr int kStatusTlasTimeoutBuild = 1;  // ... and the sequence number of the (last) build that did
 constexpr int kStatusMeshBadIndices = 2;    // rt_set_mesh_device: indices >= vertex_count, read as 0 (mesh.hip)
+constexpr int kStatusMatUndeclared = 3;     // rt_set_triangle_materials_device: ids of undeclared classes, stored as 3 (materials.hip)
 
 struct BvhBuildParams {
     const float* vertices;     // [nv][3]

@@ -16,6 +16,7 @@
 #include <sstream>
 
 #include "gaussian_tables.h"
+#include "mat_kernels.h"
 #include "rtmath.h"
 #include "toml_lite.h"
 
@@ -602,6 +603,11 @@ void rt_destroy(rt_context* ctx) {
         for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k],
                              ctx->leanTraced[k], ctx->leanDone[k]})
             if (e) (void)hipEventDestroy(e);
+    for (const rt_context::MatTable& t : ctx->matPool)
+        for (hipEvent_t e : {t.read, t.specRead})
+            if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->matSrc, ctx->matDone})
+        if (e) (void)hipEventDestroy(e);
     if (ctx->sideStream) (void)hipStreamDestroy(ctx->sideStream);
     if (ctx->leanStream) (void)hipStreamDestroy(ctx->leanStream);
     if (ctx->ownPostStream) (void)hipStreamDestroy(ctx->ownPostStream);
@@ -856,6 +862,8 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
             // a wait: launches in flight hold the old table by value, and the store is not written
             ctx->dTriMat = nullptr;
             ctx->triMatClasses = 0;
+            ctx->matDevice = false;
+            ++ctx->matSerial;
             ctx->prevVertsValid = false;  // geometry motion: the next build is a first build
         }
     }
@@ -1045,16 +1053,24 @@ int rt_set_triangle_materials(rt_context* ctx, const uint8_t* ids, uint32_t firs
     }
     // the kernels in flight read the table, and camera rays traced ahead precede it (spec_matches)
     if (int rc = sync_streams(ctx, false)) return rc;
-    if (!ctx->triMatStore) {
-        if (int rc = dalloc(ctx, &ctx->triMatStore, (size_t)ctx->capNP)) return rc;
+    // the current buffer of the pool, in place: nothing reads it now
+    rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+    ctx->matBytes = ((size_t)ctx->capNP + 15u) & ~(size_t)15u;
+    if (!tab.ids) {
+        if (int rc = dalloc(ctx, &tab.ids, ctx->matBytes)) return rc;
     }
     if (!ctx->dTriMat) {  // the first set, or the first after a reset: the reference's table
-        HIP_TRY(ctx, hipMemset(ctx->triMatStore, 3, (size_t)ctx->mesh.triCountPadded));
+        HIP_TRY(ctx, hipMemset(tab.ids, 3, ctx->matBytes));
         ctx->triMatHost.assign(n, (uint8_t)3);
         memset(ctx->triMatCount, 0, sizeof ctx->triMatCount);
         ctx->triMatCount[3] = n;
+    } else if (ctx->matDevice) {  // a device set's table: the host copy and its census afresh
+        ctx->triMatHost.assign(n, (uint8_t)3);
+        HIP_TRY(ctx, hipMemcpy(ctx->triMatHost.data(), tab.ids, n, hipMemcpyDeviceToHost));
+        memset(ctx->triMatCount, 0, sizeof ctx->triMatCount);
+        for (uint32_t k = 0; k < n; ++k) ++ctx->triMatCount[ctx->triMatHost[k]];
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->triMatStore + first, ids, count, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(tab.ids + first, ids, count, hipMemcpyHostToDevice));
     for (uint32_t k = 0; k < count; ++k) {
         uint8_t& h = ctx->triMatHost[(size_t)first + k];
         --ctx->triMatCount[h];
@@ -1062,7 +1078,9 @@ int rt_set_triangle_materials(rt_context* ctx, const uint8_t* ids, uint32_t firs
         ++ctx->triMatCount[h];
     }
     census_classes(ctx);
-    ctx->dTriMat = ctx->triMatStore;
+    ctx->dTriMat = tab.ids;
+    ctx->matDevice = false;
+    ++ctx->matSerial;
     return RT_OK;
 }
 
@@ -1072,6 +1090,108 @@ int rt_reset_triangle_materials(rt_context* ctx) {
     if (int rc = sync_streams(ctx, false)) return rc;
     ctx->dTriMat = nullptr;  // the null table: the launches of a context that never set one
     ctx->triMatClasses = 0;
+    ctx->matDevice = false;
+    ++ctx->matSerial;
+    return RT_OK;
+}
+
+// ---- the stream-ordered set (materials.hip)
+
+uint32_t rt_material_class_rule(uint32_t id) { return mat_class_of(id & 0xFFu); }
+
+// every buffer of the pool with its census, the counter and the events: the first device set
+static int ensure_mat_pool(rt_context* ctx) {
+    if (ctx->matPoolReady) return RT_OK;
+    ctx->matBytes = ((size_t)ctx->capNP + 15u) & ~(size_t)15u;
+    size_t missing = 0;
+    for (const rt_context::MatTable& t : ctx->matPool) missing += t.ids ? 0u : 1u;
+    // one block: the missing tables, then a 1-KiB census per table, then the counter's 64 bytes
+    const size_t bytes = missing * ctx->matBytes + (size_t)kMatPool * 1024 + 64;
+    uint8_t* block = nullptr;
+    if (int rc = dalloc(ctx, &block, bytes)) return rc;
+    HIP_TRY(ctx, hipMemset(block, 3, missing * ctx->matBytes));
+    HIP_TRY(ctx, hipMemset(block + missing * ctx->matBytes, 0, (size_t)kMatPool * 1024 + 64));
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));  // this first call may block; the fills precede every stream's use
+    for (hipEvent_t* e : {&ctx->matSrc, &ctx->matDone})
+        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (rt_context::MatTable& t : ctx->matPool)
+        for (hipEvent_t* e : {&t.read, &t.specRead})
+            if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    uint8_t* at = block;
+    for (rt_context::MatTable& t : ctx->matPool)
+        if (!t.ids) {
+            t.ids = at;
+            at += ctx->matBytes;
+        }
+    for (rt_context::MatTable& t : ctx->matPool) {
+        t.census = (uint32_t*)at;
+        at += 1024;
+    }
+    ctx->dMatBad = (uint32_t*)at;
+    // path traces enqueued so far read the current (host-set) table unmarked: everything on the
+    // streams their kernels run on counts as its readers
+    rt_context::MatTable& cur = ctx->matPool[ctx->matCur];
+    HIP_TRY(ctx, hipEventRecord(cur.read, ctx->stream));
+    cur.readValid = true;
+    if (ctx->sideStream) {
+        HIP_TRY(ctx, hipEventRecord(cur.specRead, ctx->sideStream));
+        cur.specValid = true;
+    }
+    ctx->matPoolReady = true;
+    return RT_OK;
+}
+
+int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* u) {
+    if (!ctx || !u) return RT_ERR_ARG;
+    const char* bad = nullptr;
+    if (!u->ids) bad = "ids must not be NULL";
+    else if (u->count == 0) bad = "count must not be 0";
+    else if ((u->classes & ~RT_MAT_CLASS_ALL) != 0u) bad = "unknown bits in classes";
+    if (bad) { ctx->err = std::string("rt_set_triangle_materials_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_set_triangle_materials_device before rt_init"; return RT_ERR_STATE; }
+    if ((uint64_t)u->first + (uint64_t)u->count > (uint64_t)ctx->mesh.triCount) {
+        ctx->err = "rt_set_triangle_materials_device: [first, first + count) must be a non-empty range of the mesh's triangles";
+        return RT_ERR_ARG;
+    }
+    if (int rc = ensure_mat_pool(ctx)) return rc;
+    // On the stream of the vertex updates: the side stream of a pipelined context, where the next
+    // frame's shade kernel follows it without an event and it runs beside the current frame's chain.
+    hipStream_t s = ctx->postStream ? ctx->sideStream : ctx->stream;
+    const int next = (ctx->matCur + 1) % kMatPool;
+    rt_context::MatTable& dst = ctx->matPool[next];
+    if (u->ready_event) {
+        HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)u->ready_event, 0));
+    } else if (s != ctx->stream) {
+        HIP_TRY(ctx, hipEventRecord(ctx->matSrc, ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->matSrc, 0));
+    }
+    // the launches that still read the buffer this set writes; the previous table was written on this
+    // stream (an earlier device set) or behind a wait for every stream (a host set)
+    if (dst.readValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.read, 0));
+    if (dst.specValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.specRead, 0));
+    MatSetParams p;
+    p.prev = ctx->dTriMat;  // null after rt_set_mesh* and a reset: 3 everywhere
+    p.src = u->ids;
+    p.dst = dst.ids;
+    p.census = dst.census;
+    p.badCount = ctx->dMatBad;
+    p.status = ctx->status;
+    p.first = u->first;
+    p.count = u->count;
+    p.triCount = ctx->mesh.triCount;
+    p.capBytes = (uint32_t)ctx->matBytes;
+    p.classes = u->classes;
+    HIP_TRY(ctx, rtk_launch_mat_set(&p, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->matDone, s));
+    // the caller's later work on the context stream follows the read of its buffer, and so does every
+    // later path trace: its kernels run on this stream, on the context stream or behind a fork of it
+    if (s != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->matDone, 0));
+    dst.readValid = dst.specValid = false;
+    ctx->matCur = next;
+    ctx->dTriMat = dst.ids;
+    ctx->triMatClasses = u->classes;  // the plan of later frames: exactly the declared bits
+    ctx->matDevice = true;
+    ++ctx->matSerial;
     return RT_OK;
 }
 
@@ -1353,6 +1473,7 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
         case RT_ARR_PT_Q4_ORIGINS:
         case RT_ARR_PT_Q4_DIRS: return (size_t)ctx->fr.ws.cap * 16;
         case RT_ARR_TRI_MATERIALS: return (size_t)ctx->mesh.triCount;
+        case RT_ARR_TRI_MATERIAL_CENSUS: return 256 * sizeof(uint32_t);
         default: return 0;
     }
 }
@@ -1421,6 +1542,20 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
             if (!ctx->dTriMat) { memset(dst, 3, n); return RT_OK; }
             if (int rc = sync_streams(ctx)) return rc;
             HIP_TRY(ctx, hipMemcpy(dst, ctx->dTriMat, n, hipMemcpyDeviceToHost));
+            return RT_OK;
+        }
+        case RT_ARR_TRI_MATERIAL_CENSUS: {  // triangles per id of that table: the device set's census, else the host's
+            uint32_t* out = (uint32_t*)dst;
+            if (bytes < 256 * sizeof(uint32_t)) { ctx->err = "destination too small"; return RT_ERR_ARG; }
+            if (!ctx->dTriMat) {
+                memset(out, 0, 256 * sizeof(uint32_t));
+                out[3] = ctx->mesh.triCount;
+            } else if (ctx->matDevice) {
+                if (int rc = sync_streams(ctx)) return rc;
+                HIP_TRY(ctx, hipMemcpy(out, ctx->matPool[ctx->matCur].census, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            } else {
+                memcpy(out, ctx->triMatCount, 256 * sizeof(uint32_t));
+            }
             return RT_OK;
         }
         default: ctx->err = "unknown array"; return RT_ERR_ARG;

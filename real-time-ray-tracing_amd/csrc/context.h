@@ -55,6 +55,11 @@ struct BvhBufs {
 #endif
 constexpr int kGbSets = RTX_GB_SETS;  // G-buffer / camera-output sets in flight with frame pipelining
 
+// Material-table buffers (rt_context::matPool).  Any size >= 2 is correct, since a device set waits
+// on the device for the readers of the buffer it writes; with 4, a host that sets once per frame
+// writes the buffer last read three frames back, whose path trace ended long before.
+constexpr int kMatPool = 4;
+
 struct FrameResources {
     bool ready = false;
     // sky / sun (kernel.cu:280-307)
@@ -120,6 +125,7 @@ struct FrameResources {
         bool shade = false;  // the shade kernel went ahead too
         int block = 0;
         uint64_t epoch = 0;  // the geometry epoch of the LBVH they were traced on
+        uint64_t matSerial = 0;  // rt_context::matSerial of the material table they read
         PathTraceParams p{};
     } spec;
     bool specReady = false;          // set 1's buffers and the events exist (ensure_sync_spec)
@@ -320,14 +326,33 @@ struct rt_context {
     bool dispValid[2] = {false, false};   // set k's build recorded a displacement (bvh[k].triDisp)
     bool dispTraced[2] = {false, false};  // ... and a path trace has applied it: later ones on that build do not
     // per-triangle materials (rt_set_triangle_materials): null until the first set and after a reset,
-    // and then every launch is the one of a context without the feature.  triMatStore keeps the
+    // and then every launch is the one of a context without the feature.  The pool below keeps the
     // allocation across resets; the host copy gives the census of ids (triMatCount) and from it the
     // kernel classes (rt_material_classes) without a device read
-    uint8_t* dTriMat = nullptr;         // [triCountPadded], 3 past what was set
-    uint8_t* triMatStore = nullptr;
+    uint8_t* dTriMat = nullptr;         // the current table (matPool[matCur].ids) or null; 3 past what was set
     std::vector<uint8_t> triMatHost;    // [triCount]
     uint32_t triMatCount[256] = {};     // triangles per id
-    uint32_t triMatClasses = 0;         // RT_MAT_CLASS_* bits of the ids present
+    uint32_t triMatClasses = 0;         // RT_MAT_CLASS_* bits of the ids present (after a device set: as declared)
+    // The tables (rt_set_triangle_materials_device, materials.hip).  Launches hold
+    // their table's address by value, so a device set never writes the current table: it writes the
+    // next buffer of this pool, in turn, behind the events of the path traces that read that buffer
+    // (waited for on the device).  The host setters write the current buffer in place, after their
+    // wait for every stream, and allocate that buffer only; the first device set allocates the rest.
+    struct MatTable {
+        uint8_t* ids = nullptr;         // [matBytes]: every byte an id, 3 where nothing was set
+        uint32_t* census = nullptr;     // [256] triangles per id over [0, triCount), of the last device set into it
+        hipEvent_t read = nullptr;      // behind the last path trace that read it, on the context stream
+        hipEvent_t specRead = nullptr;  // behind the last shade kernel a synchronous draw launched ahead on it (side stream)
+        bool readValid = false, specValid = false;
+    } matPool[kMatPool];
+    int matCur = 0;
+    size_t matBytes = 0;                // capNP rounded up to 16
+    bool matPoolReady = false;          // every buffer, census and event exists (the first device set)
+    bool matDevice = false;             // the current table is a device set's: the host copy and census are stale
+    uint64_t matSerial = 0;             // +1 per change of the table (spec_matches: addresses are recycled)
+    uint32_t* dMatBad = nullptr;        // k_mat_set's count of undeclared ids, zero between sets
+    hipEvent_t matSrc = nullptr;        // the context stream's work up to a set without a ready event
+    hipEvent_t matDone = nullptr;       // the last device set's end
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
     // and the setters that change the stream drain it), and on a context without a post stream the

@@ -378,7 +378,14 @@ int check_device_status(rt_context* ctx) {
         ctx->err = "rt_set_mesh_device: " + std::to_string(badIdx) + " index(es) not below vertex_count were read as 0";
         return RT_ERR_DEVICE;
     }
-    const uint32_t missing = __atomic_load_n(&ctx->status[kStatusTlasTimeout], __ATOMIC_ACQUIRE);
+    // rt_set_triangle_materials_device: ids whose class the caller did not declare, stored as 3 (materials.hip)
+    if (const uint32_t badIds = __atomic_load_n(&ctx->status[kStatusMatUndeclared], __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(&ctx->status[kStatusMatUndeclared], 0u, __ATOMIC_RELEASE);
+        ctx->err = "rt_set_triangle_materials_device: " + std::to_string(badIds) +
+                   " id(s) of a class not declared were stored as 3";
+        return RT_ERR_DEVICE;
+    }
+    const uint32_t missing =__atomic_load_n(&ctx->status[kStatusTlasTimeout], __ATOMIC_ACQUIRE);
     if (!missing) return RT_OK;
     const uint32_t build = __atomic_load_n(&ctx->status[kStatusTlasTimeoutBuild], __ATOMIC_ACQUIRE);
     if (ctx->sideStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->sideStream));
@@ -764,13 +771,16 @@ bool spec_on(const rt_context* ctx) {
 
 // whether the camera and shade kernels launched with `a` wrote what ones launched with `b` would:
 // the same parameters but for those they do not read (or that only select the later kernels)
-bool spec_matches(const PathTraceParams& a, uint64_t epochA, const PathTraceParams& b, uint64_t epochB) {
+bool spec_matches(const PathTraceParams& a, uint64_t epochA, uint64_t matA, const PathTraceParams& b, uint64_t epochB,
+                  uint64_t matB) {
     // they read the LBVH set of the frame that launched them, the next frame reads the other: both
     // hold the same build (tests/test_gpu_bvh.py) exactly when no vertex update came between them
     if (epochA != epochB) return false;
-    // the triangle materials need no field here: rt_set_triangle_materials and its reset wait for the
-    // streams like every setter, and sync_streams drops what was traced ahead, so a launch that is
-    // still kept read the table (triMat's contents, not only its address) the next frame reads
+    // the triangle materials: rt_set_triangle_materials and its reset wait for the streams like every
+    // setter, and sync_streams drops what was traced ahead; rt_set_triangle_materials_device does not,
+    // and the tables' buffers are recycled, so triMat's address does not tell its contents: the
+    // table's serial does
+    if (matA != matB) return false;
     PathTraceParams x = a, y = b;
     for (PathTraceParams* q : {&x, &y}) {
         q->rayCounter = nullptr;  // the launches ahead count into specRayCounter
@@ -885,7 +895,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     if (fr.spec.valid) {
         fr.spec.valid = false;
         HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->specDone, 0));
-        reuse = !side && spec_matches(p, ctx->geomEpoch, fr.spec.p, fr.spec.epoch);
+        reuse = !side && spec_matches(p, ctx->geomEpoch, ctx->matSerial, fr.spec.p, fr.spec.epoch, fr.spec.matSerial);
         reuseShade = reuse && fr.spec.shade;
         if (!reuse) p.ws.countersZeroed = 0;  // their counts are in the block: the launcher clears it
         fr.specCounts = reuse ? 1 : 2;  // folded into the frame's (or cleared) ahead of the next ones
@@ -938,6 +948,13 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     // pending only once the launches that store it are enqueued: a failed launch leaves the next
     // serial frame to ask again instead of freezing the chain choice
     if (askQ3) fr.q3Pending = true;
+    // the material table this path trace read, marked behind its last reading kernel: the shade kernel
+    // on the side stream and the forked lean pass are joined into the context stream above
+    if (p.triMat && ctx->matPoolReady) {
+        rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+        HIP_TRY(ctx, hipEventRecord(tab.read, ctx->stream));
+        tab.readValid = true;
+    }
     if (p.triDisp) ctx->dispTraced[ctx->bvhSet] = true;  // later path traces on this build see no motion of the geometry
     if (!ctx->postStream) {  // block b + 2 is zeroed by this frame's resolve, enqueued above
         const int b = fr.syncIdx;
@@ -1242,11 +1259,17 @@ int launch_spec_camera(rt_context* ctx) {
         HIP_TRY(ctx, rtk_launch_pt_shade(&p, ctx->sideStream, nullptr));
     }
     HIP_TRY(ctx, hipEventRecord(ctx->specDone, ctx->sideStream));
+    if (shade && p.triMat && ctx->matPoolReady) {  // the table that shade kernel reads (rt_set_triangle_materials_device)
+        rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+        HIP_TRY(ctx, hipEventRecord(tab.specRead, ctx->sideStream));
+        tab.specValid = true;
+    }
     fr.syncZeroed[b] = false;
     fr.spec.valid = true;
     fr.spec.shade = shade;
     fr.spec.block = b;
     fr.spec.epoch = ctx->geomEpoch;  // of this frame's LBVH, built or checked by enqueue_frame just before
+    fr.spec.matSerial = ctx->matSerial;
     fr.spec.p = p;
     return RT_OK;
 }

@@ -27,7 +27,7 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            SUN_PDF=22, SUN_CDF=23, SUN_DIR=24, HISTOGRAM=25, EXPOSURE=26, COLOR4=27, COLOR16=28, COLOR64=29,
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
-           BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44)
+           BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44, TRI_MATERIAL_CENSUS=45)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
@@ -108,6 +108,12 @@ class Mesh(C.Structure):
                 ("triangle_count", C.c_uint32), ("ready_event", C.c_void_p)]
 
 
+class MaterialUpdate(C.Structure):
+    """rt_material_update: one device material set (rt_set_triangle_materials_device)."""
+    _fields_ = [("ids", C.c_void_p), ("first", C.c_uint32), ("count", C.c_uint32), ("classes", C.c_uint32),
+                ("ready_event", C.c_void_p)]
+
+
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
 
@@ -178,8 +184,11 @@ SIGNATURES = {
     "rt_set_triangle_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rt_reset_triangle_materials": (C.c_int, [C.c_void_p]),
     "rt_material_classes": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rt_set_triangle_materials_device": (C.c_int, [C.c_void_p, C.POINTER(MaterialUpdate)]),
+    "rt_material_class_rule": (C.c_uint32, [C.c_uint32]),
 }
 MAT_CLASS_GLOSSY, MAT_CLASS_MICROFACET = 1, 2  # RT_MAT_CLASS_*
+MAT_CLASS_ALL = MAT_CLASS_GLOSSY | MAT_CLASS_MICROFACET
 IMAGE_PPM_RGBA8, IMAGE_PFM_HDR = 0, 1
 DRAW_ASYNC = 1  # rt_draw_device flag
 BUF_SET1, BUF_SET2, BUF_SET3 = 0x100, 0x200, 0x300  # rt_bind_buffer: further G-buffer sets (frame pipelining)
@@ -456,6 +465,20 @@ class RayTracer:
             raise ValueError("set_triangle_materials: first and the triangle count must fit 32 bits")
         self._check(self.lib.rt_set_triangle_materials(self.h, ids.ctypes.data, int(first), len(ids)),
                     "rt_set_triangle_materials")
+
+    def set_triangle_materials_device(self, ptr: int, count: int, first: int = 0, classes: int = MAT_CLASS_ALL,
+                                      ready_event: int | None = None):
+        """The same from device memory (count uint8 ids at ptr, any alignment), stream-ordered: no
+        host wait.  classes: the MAT_CLASS_* bits that bound the classes of every id of the whole
+        table after the update (material_classes() of it; declaring more costs speed only, an id of
+        an undeclared class is stored as 3 and reported by the next checking call).  ready_event as
+        in update_vertices_device."""
+        if not 0 <= int(first) <= 0xFFFFFFFF or not 0 <= int(count) <= 0xFFFFFFFF:
+            raise ValueError("set_triangle_materials_device: first and count must fit 32 bits")
+        if not 0 <= int(classes) <= 0xFFFFFFFF:
+            raise ValueError("set_triangle_materials_device: classes must fit 32 bits")
+        u = MaterialUpdate(ptr, int(first), int(count), int(classes), ready_event)
+        self._check(self.lib.rt_set_triangle_materials_device(self.h, C.byref(u)), "rt_set_triangle_materials_device")
 
     def reset_triangle_materials(self):
         """Back to the reference's table, material 3 for every triangle."""

@@ -24,7 +24,10 @@ material class.
 
 Writes profiles/materials.json.
 
-Usage: python tools/material_probe.py [--frames 100] [--repeats 5] [--out PATH]"""
+With --device-sets: the table re-set ahead of every frame through rt_set_triangle_materials_device,
+through the host setter, and not at all (device_sets below); writes profiles/materials_device.json.
+
+Usage: python tools/material_probe.py [--device-sets] [--frames 100] [--repeats 5] [--out PATH]"""
 import argparse
 import json
 import os
@@ -55,14 +58,106 @@ def tables(n):
                 mix8=hashed(n, MIX8))
 
 
+def device_sets(a):
+    """--device-sets: what re-setting the whole table every frame costs a pipelined 1080p frame, four
+    ways in ONE context, timed in turn --repeats times (medians of ms per frame):
+
+      device   rt_set_triangle_materials_device ahead of every frame, two tables of the same classes
+               (mix8 and its reverse) alternating, the ids resident on the device, with the ready
+               event of their upload (the set runs beside the previous frame's trace chain)
+      device_no_event  the same with ready_event NULL: the read follows the context stream's work,
+               the previous frame's trace chain included
+      host     the same through rt_set_triangle_materials, which drains the pipeline every frame
+      none     no set at all: the frames under the table the last series left
+
+    Writes profiles/materials_device.json."""
+    import torch
+
+    import rtx
+    from rtx.frames import FramePipeline
+
+    w, h, spp = 1920, 1080, 4
+    dev = torch.device("cuda", 0)
+    prev = torch.cuda.current_stream(0)
+    rt = rtx.RayTracer(w, h, rtx.write_config(os.path.join(tempfile.mkdtemp(), "m.toml"), w, h, spp=spp)).init()
+    try:
+        rt.set_delta_time(16.667)
+        cam = rt.camera
+        cam.pos[:] = TERRAIN_CAM["pos"]
+        cam.yaw, cam.pitch = TERRAIN_CAM["yaw"], TERRAIN_CAM["pitch"]
+        rt.camera = cam
+        n = int(rt.info().triCount)
+        host = [hashed(n, MIX8), hashed(n, MIX8)[::-1].copy()]
+        classes = rtx.material_classes(host[0])
+        assert classes == rtx.material_classes(host[1])
+        resident = [torch.from_numpy(t).to(dev) for t in host]
+        ready = torch.cuda.Event()
+        ready.record(prev)
+        torch.cuda.synchronize()
+        fp = FramePipeline(rt, dev, pipelined=True)
+        state = dict(f=0)
+
+        def run(mode, frames):
+            for _ in range(frames):
+                state["f"] += 1
+                k = state["f"] & 1
+                if mode == "device":
+                    rt.set_triangle_materials_device(resident[k].data_ptr(), n, 0, classes, ready.cuda_event)
+                elif mode == "device_no_event":
+                    rt.set_triangle_materials_device(resident[k].data_ptr(), n, 0, classes)
+                elif mode == "host":
+                    rt.set_triangle_materials(host[k])
+                fp.frame(state["f"])
+            fp.finish()
+
+        modes = ("device", "device_no_event", "host", "none")
+        series = {m: [] for m in modes}
+        for _ in range(a.repeats):
+            for m in modes:
+                run(m, a.warmup)
+                t0 = time.perf_counter()
+                run(m, a.frames)
+                series[m].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        run("device", 3)
+        assert np.array_equal(rt.download("TRI_MATERIALS"), host[state["f"] & 1])
+        assert np.array_equal(rt.download("TRI_MATERIAL_CENSUS", np.uint32), np.bincount(host[0], minlength=256))
+        errors = int(rt.download("PT_QUEUE", np.uint32)[10])
+    finally:
+        rt.cleanup()
+        torch.cuda.set_stream(prev)
+    rows = {m: dict(ms_per_frame=float(np.median(series[m])), series_ms=series[m]) for m in modes}
+    for m in modes:
+        rows[m]["over_none_ms"] = rows[m]["ms_per_frame"] - rows["none"]["ms_per_frame"]
+    res = dict(device=torch.cuda.get_device_name(0),
+               config="%dx%d, %d spp, terrain camera %r, pipelined FramePipeline, LBVH rebuild every frame, %d triangles, "
+                      "the whole table (mix8 / its reverse, classes %d) set ahead of every frame" % (w, h, spp, TERRAIN_CAM, n, classes),
+               method="one context; the four modes timed in turn %d times, %d frames each after %d warm-up frames; "
+                      "ms_per_frame is the median of the series, host time per frame with one wait at the end of a series"
+                      % (a.repeats, a.frames, a.warmup),
+               internal_errors=errors, modes=rows,
+               host_minus_device_ms=rows["host"]["ms_per_frame"] - rows["device"]["ms_per_frame"])
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "materials_device.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "materials.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--marked", type=int, default=20, help="frames whose kernels are bracketed by events")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "materials.json"))
+    ap.add_argument("--device-sets", action="store_true",
+                    help="time the table re-set every frame: device call, host setter, no set (profiles/materials_device.json)")
+    ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
+    if a.device_sets:
+        return device_sets(a)
     import torch
 
     import rtx
