@@ -3,7 +3,7 @@
 // Restates, per BLAS batch of 1024 triangles:
 //   UpdateSceneGeometry<256,4>  updateGeometry.cuh:63-262
 //   RadixSort<256,4>            radixSort.cuh:19-246   (== stable sort by 32-bit key)
-//   BuildLBVH<256,4>            buildBVH.cuh:16-271    (Karras 2012, no tie-break)
+//   BuildLBVH<256,4>            buildBVH.cuh:16-271    (Karras 2012; tie-break added, see lcp)
 // and for the TLAS over the BLAS roots:
 //   UpdateTLAS<256,4,1024>      updateGeometry.cuh:264-364 (incl. the missing +32 merge)
 // sequenced as BuildBvhLevel1/2 (bvh.cu:7-97).  The per-frame memsets of morton/tlasMorton
@@ -35,10 +35,13 @@ static uint32_t morton_of(F3 c, const AABB& scene) {
 
 static int clz32(uint32_t v) { return v == 0 ? 32 : __builtin_clz(v); }
 
-// LCP, buildBVH.cuh:8-14
-static int lcp(const uint32_t* m, int n, uint32_t m0, int j) {
+// LCP, buildBVH.cuh:8-14, with Karras's tie-break (DESIGN.md deviation 15): equal keys compare by
+// their sorted positions, delta = 32 + clz(i ^ j).  The reference has none; on a run of three or
+// more equal keys its nodes form a cycle.  Distinct keys and runs of two give the same tree.
+static int lcp(const uint32_t* m, int n, int i, uint32_t m0, int j) {
     if (j < 0 || j >= n) return 0;
-    return clz32(m0 ^ m[j]);
+    const uint32_t x = m0 ^ m[j];
+    return x == 0 ? 32 + clz32((uint32_t)(i ^ j)) : clz32(x);
 }
 
 // Karras topology + bottom-up boxes for one batch (buildBVH.cuh:60-267).  Boxes are a pure
@@ -54,24 +57,24 @@ static void build_lbvh(Node* nodes, const AABB* leafBoxes, const uint32_t* morto
     }
     for (int i = 0; i < n - 1; ++i) {
         uint32_t m0 = morton[i];
-        int dl = lcp(morton, n, m0, i - 1);
-        int dr = lcp(morton, n, m0, i + 1);
+        int dl = lcp(morton, n, i, m0, i - 1);
+        int dr = lcp(morton, n, i, m0, i + 1);
         int d = (dr - dl) >= 0 ? 1 : -1;
-        int deltaMin = lcp(morton, n, m0, i - d);
+        int deltaMin = lcp(morton, n, i, m0, i - d);
         int lmax = 2;
-        while (lcp(morton, n, m0, i + lmax * d) > deltaMin) lmax *= 2;
+        while (lcp(morton, n, i, m0, i + lmax * d) > deltaMin) lmax *= 2;
         int l = 0;
         for (int t = lmax / 2; t >= 1; t /= 2)
-            if (lcp(morton, n, m0, i + (l + t) * d) > deltaMin) l += t;
+            if (lcp(morton, n, i, m0, i + (l + t) * d) > deltaMin) l += t;
         int j = i + l * d;
-        int deltaNode = lcp(morton, n, m0, j);
+        int deltaNode = lcp(morton, n, i, m0, j);
         // split search; the reference loops while ceil(l/div) >= 1 (only int overflow ends
         // it) — the extra t == 1 probes are no-ops, so stop after the first t == 1.
         int s = 0;
         int div = 2;
         while (true) {
             int t = (l + div - 1) / div;
-            if (lcp(morton, n, m0, i + (s + t) * d) > deltaNode) s += t;
+            if (lcp(morton, n, i, m0, i + (s + t) * d) > deltaNode) s += t;
             if (t <= 1) break;
             div *= 2;
         }

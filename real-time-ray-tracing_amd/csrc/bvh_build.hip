@@ -13,7 +13,9 @@
 //   * sort: stable LSD radix on the low 30 bits (all codes < 2^30; padding keys
 //     0xFFFFFFFF sit at the highest positions, so stability keeps them last) == the
 //     reference's stable 32-bit sort (radixSort.cuh:19-246)
-//   * Karras: the reference's LCP/direction/split rules (buildBVH.cuh:8-134)
+//   * Karras: the reference's LCP/direction/split rules (buildBVH.cuh:8-134), plus the tie-break
+//     on sorted positions for equal keys that the reference lacks (lcp; the same tree wherever
+//     no key occurs three times, a valid tree where the reference's is a cycle)
 //   * boxes: a pure function of the topology; evaluated by atomic bottom-up climbing in LDS
 //   * TLAS scene box: the reference's reduction skips thread slots s with s mod 64 >= 32
 //     (no +32 merge, updateGeometry.cuh:317-336), i.e. batches b with (b & 255) >= 128.
@@ -249,38 +251,45 @@ RT_DEV void radix_sort(Lds<kThr>& s) {
 }
 
 // delta(i, j) of the reference (buildBVH.cuh:8-20): the common prefix length of key i (m0) and key j,
-// 32 for equal keys, 0 for j outside [0, n).  Branch-free: the read is clamped into the array and
-// the out-of-range result selected afterwards.
-RT_DEV int lcp(const uint32_t* key, int n, uint32_t m0, int j) {
+// 0 for j outside [0, n) — and, where the reference has 32 for equal keys, Karras's tie-break on the
+// sorted positions, 32 + clz(i ^ j) (DESIGN.md deviation 15): without it a run of three or more
+// equal keys links its nodes into a cycle.  Distinct keys and runs of two compare as before.
+// Branch-free: the read is clamped into the array and the out-of-range result selected afterwards
+// (a clamped j can equal i; that 64 is never the result).  The two cases are one 64-bit count, so
+// the position half is issued under the LDS read and three VALU operations follow it, as before.
+RT_DEV int lcp(const uint32_t* key, int n, int i, uint32_t m0, int j) {
     const int jc = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
     const uint32_t x = m0 ^ key[jc];
-    const int c = x == 0u ? 32 : __builtin_clz(x);
+    const uint64_t xy = ((uint64_t)x << 32) | (uint32_t)(i ^ jc);  // x == 0 ? 32 + clz(i ^ jc) : clz(x)
+    const int c = xy == 0u ? 64 : __builtin_clzll(xy);
     return (uint32_t)j < (uint32_t)n ? c : 0;
 }
 
 // Karras 2012 topology over key1[0..n) (buildBVH.cuh:60-134) of internal node i, into the info
-// words; also clears node i's arrival count for the refit.  The probes i + k * d (d = +-1) are
+// words; also clears node i's arrival count for the refit.  Every delta is lcp's, tie-break
+// included, so the n - 1 nodes form one tree over the n leaves whatever keys repeat (the BLAS, the
+// one-wave TLAS and the workgroup TLAS all come through here).  The probes i + k * d (d = +-1) are
 // 24-bit multiplies (v_mul_i32_i24, full rate; |k| < 2048) and the split search's ceil(l / div),
 // div = 2, 4, 8 ..., a shift: the reference's arithmetic on these operand ranges.
 template <int kThr>
 RT_DEV void karras_node(Lds<kThr>& s, int n, int i) {
     const uint32_t* key = s.key1;
     const uint32_t m0 = key[i];
-    const int dl = lcp(key, n, m0, i - 1);
-    const int dr = lcp(key, n, m0, i + 1);
+    const int dl = lcp(key, n, i, m0, i - 1);
+    const int dr = lcp(key, n, i, m0, i + 1);
     const int d = (dr - dl) >= 0 ? 1 : -1;
-    const int deltaMin = lcp(key, n, m0, i - d);
+    const int deltaMin = lcp(key, n, i, m0, i - d);
     int lmax = 2;
-    while (lcp(key, n, m0, i + __mul24(lmax, d)) > deltaMin) lmax *= 2;
+    while (lcp(key, n, i, m0, i + __mul24(lmax, d)) > deltaMin) lmax *= 2;
     int l = 0;
     for (int t = lmax >> 1; t >= 1; t >>= 1)
-        if (lcp(key, n, m0, i + __mul24(l + t, d)) > deltaMin) l += t;
+        if (lcp(key, n, i, m0, i + __mul24(l + t, d)) > deltaMin) l += t;
     const int j = i + __mul24(l, d);
-    const int deltaNode = lcp(key, n, m0, j);
+    const int deltaNode = lcp(key, n, i, m0, j);
     int sp = 0, sh = 1;  // div = 2^sh
     while (true) {  // the reference's extra t == 1 probes are no-ops (SURVEY §0 #8b)
         const int t = (l + (1 << sh) - 1) >> sh;  // (l + div - 1) / div, l >= 0
-        if (lcp(key, n, m0, i + __mul24(sp + t, d)) > deltaNode) sp += t;
+        if (lcp(key, n, i, m0, i + __mul24(sp + t, d)) > deltaNode) sp += t;
         if (t <= 1) break;
         ++sh;
     }

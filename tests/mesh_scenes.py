@@ -94,6 +94,97 @@ SHAPES = {
 ORDER = ("grid1025", "soup2", "fan5000", "grid1023", "top_digit", "gaps", "grid1024", "soup2")
 
 
+def stack(layers, ntri):
+    """layers coincident copies of grid(ntri), each with its own vertices, layer after layer: every
+    Morton key of the batch occurs layers times."""
+    v, idx = grid(ntri)
+    vs = np.concatenate([v] * layers)
+    ids = np.concatenate([idx + np.uint32(k * len(v)) for k in range(layers)])
+    return np.ascontiguousarray(vs, np.float32), np.ascontiguousarray(ids, np.uint32)
+
+
+# `runs`: copies of one small triangle at sites along x.  Only x differs between the sites, so the
+# sorted order is the sites' order, and 601 sites on 1023 Morton cells have distinct keys.
+RUN_TRI = np.asarray([(0.0, 0.0, 0.0), (0.3, 0.05, 0.0), (0.0, 0.1, 0.3)], np.float32)
+RUN_SITES = 601
+# site -> copies.  Sorted positions: the runs of 3, 4 and 7 lie inside one 64-lane wave (10..12,
+# 102..105, 205..211), the run of 63 fills all but one lane of a wave (320..382), the run of 64
+# straddles two (473..536), those of 65 and 200 exceed one (636..700, 750..949).
+RUNS = {10: 3, 100: 4, 200: 7, 309: 63, 400: 64, 500: 65, 550: 200}
+RUNS_ENDS = {0: 3, 100: 4, 200: 7, 309: 63, 400: 64, 500: 65, 550: 200, 600: 5}
+
+
+def runs(lengths=None, drop=0, vertex0_at=None, seed=7):
+    """One batch: lengths[s] copies of RUN_TRI at site s (one copy elsewhere), in a seeded shuffle,
+    each triangle with its own vertices; the first `drop` single sites stay empty.  vertex0_at: an
+    extra, unreferenced vertex 0 at that site's centroid, where the padding triangles of a count
+    that is no multiple of 4 then lie: they sort into that site's run."""
+    lengths = RUNS if lengths is None else lengths
+    sites = []
+    for s in range(RUN_SITES):
+        if s not in lengths and drop > 0:
+            drop -= 1
+            continue
+        sites += [s] * lengths.get(s, 1)
+    sites = np.random.default_rng(seed).permutation(np.asarray(sites))
+    off = np.zeros((len(sites), 1, 3), np.float32)
+    off[:, 0, 0] = sites.astype(np.float32) * np.float32(0.5)
+    v = (RUN_TRI[None] + off).reshape(-1, 3)
+    idx = np.arange(3 * len(sites), dtype=np.uint32).reshape(-1, 3)
+    if vertex0_at is not None:
+        c = (RUN_TRI[0] + RUN_TRI[1] + RUN_TRI[2]) / np.float32(3.0)
+        c[0] += np.float32(vertex0_at) * np.float32(0.5)
+        v, idx = np.concatenate([c[None], v]), idx + np.uint32(1)
+    return np.ascontiguousarray(v, np.float32), np.ascontiguousarray(idx, np.uint32)
+
+
+def speck():
+    """grid(1000) shrunk to a 0.0115 x 0.011 patch (heights kept) beside one 100-unit triangle: the
+    patch lies in one Morton cell of x and of z, so about half of its keys repeat; 1,001 triangles,
+    so three padding triangles at vertex 0 sort among them."""
+    v, idx = grid(1000)
+    v = v * np.asarray([0.001, 1.0, 0.001], np.float32)
+    big = np.asarray([(-50.0, -1.0, -50.0), (50.0, -1.0, -50.0), (0.0, -1.0, 50.0)], np.float32)
+    n = np.uint32(len(v))
+    return (np.ascontiguousarray(np.concatenate([v, big]), np.float32),
+            np.concatenate([idx, np.asarray([(n, n + 1, n + 2)], np.uint32)]))
+
+
+def all_equal():
+    """1,024 times the same triangle, in the plane y = 0: one key, and a batch box without height."""
+    v = np.asarray([(0, 0, 0), (1, 0, 0), (0, 0, 1)], np.float32)
+    return v, np.tile(np.asarray([(0, 1, 2)], np.uint32), (1024, 1))
+
+
+def flat(y):
+    """grid(1000) with every height y: no extent on one axis, so the Morton quotient there is 0 / 0."""
+    v, idx = grid(1000)
+    v = v.copy()
+    v[:, 1] = np.float32(y)
+    return v, idx
+
+
+# meshes with Morton keys that occur three times and more (one batch, the last with padding
+# triangles, a degenerate batch box, equal TLAS keys on the one-wave and the workgroup path), and two
+# flat meshes without duplicates
+DUPLICATE_SHAPES = {
+    "stack3": lambda: stack(3, 340),
+    "stack5": lambda: stack(5, 204),
+    "runs": runs,
+    "runs_ends": lambda: runs(RUNS_ENDS, drop=4),
+    "runs_pad": lambda: runs(drop=3, vertex0_at=309),
+    "speck": speck,
+    "all_equal": all_equal,
+    "tlas3": lambda: stack(3, 1024),
+    "tlas66": lambda: stack(66, 1024),
+    "flat0": lambda: flat(0.0),
+    "flat_neg": lambda: flat(-3.0),
+}
+# shrinks after growing; tlas66 (67,584 triangles) has a context of its own
+DUPLICATE_ORDER = ("stack3", "tlas3", "runs", "all_equal", "speck", "runs_pad", "stack5", "flat0", "runs_ends",
+                   "flat_neg", "stack3")
+
+
 def welded_cube():
     """[-1, 1]^3 as material_scenes.cube_triangles lays it out (6 faces of 8 x 8 quads, 768 triangles
     in the same order) with each face's 81 vertices shared: (6 * 81 vertices, 768 index triples)."""
