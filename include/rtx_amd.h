@@ -484,6 +484,69 @@ int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* 
  * it to rt_material_classes.  No context needed. */
 uint32_t rt_material_class_rule(uint32_t id);
 
+/* The material table: what a material id means.  Ids are 0..255 (the range of the per-triangle
+ * table's uint8).  rt_default_material(id) is the reference's meaning of the id (init.cu:215-251 over
+ * the SurfaceMaterial defaults): the type of ids 0..9 as listed above and RT_MAT_MIRROR for 10..255,
+ * flags 0, color 1, emission 0, ior 1.33f, alpha 0.05f, f0 (0.56f, 0.57f, 0.58f); host only, no
+ * context.  Before the first rt_set_materials and after rt_reset_materials the context has no custom
+ * table: rt_get_materials returns the defaults and the path trace launches exactly the kernels it
+ * launched before these calls existed.  rt_set_materials replaces entries [first_id, first_id + count)
+ * and leaves the others as they were (the defaults, on the first call).
+ *
+ * Shading, each rule the identity at the default values, bit for bit:
+ *   diffuse types (Lambertian, microfacet), flags 0: albedo = (triplanar soil albedo) * color,
+ *     component-wise, once, behind the three-plane sum and ahead of every use of the albedo;
+ *   RT_MAT_FLAG_FLAT: no texture at all: albedo = color and the shading normal stays the hit's
+ *     interpolated smooth normal; light sampling, MIS and the throughput are unchanged code;
+ *   microfacet: f0 and alpha are the entry's; glass: etaT = ior; mirror: no parameter;
+ *   emissive: a path that ends on the hit (a camera or bounce ray, not an occluded shadow ray) carries
+ *     `emission` where a sky hit carries the environment, ahead of the path tracer's clamp at 10.
+ *     Emitters are NOT sampled as lights: next-event estimation of emissive triangles is out of scope,
+ *     shadow rays towards the sun or sky that hit an emitter stay occluded, and an emitter lights the
+ *     scene only through the bounce rays that land on it.
+ * The mask of RT_BUF_RENDER_COLOR stays the id, and [render] materialOverride still chooses the id,
+ * whose entry then supplies the parameters (its low 8 bits index the table).
+ *
+ * Kernels: while a custom table is active every frame runs one table-reading variant of the shading
+ * kernels, instantiated on the all-classes (glossy and microfacet) kernels only, on the unsplit
+ * four-kernel bounce plan; the class of an id follows its entry's type, so rt_material_classes no
+ * longer selects anything and rt_set_triangle_materials_device records RT_MAT_CLASS_ALL as the
+ * declared classes (its kernel replaces and counts nothing).  This is deliberate: one new
+ * instantiation per kernel instead of one per class combination.  It costs a Lambertian-only custom
+ * table some speed and no pixel.  After a later rt_reset_materials a device-set triangle table keeps
+ * the all-classes kernels until ids are set again.
+ *
+ * rt_set_materials and rt_reset_materials behave like rt_set_triangle_materials: they wait for the
+ * renderer's streams, drop what a synchronous draw traced ahead and take effect for every path trace
+ * enqueued afterwards; they are not stream-ordered.  The table belongs to the context, not the mesh:
+ * rt_set_mesh* resets the per-triangle ids to 3 and leaves it alone.  Every rank of a multi-GPU run
+ * calls with the same data.  The first rt_set_materials allocates the device table (256 records of
+ * 64 bytes).
+ * On any error nothing changes.  Checked in this order: RT_ERR_ARG for NULL ctx, m or out, count == 0,
+ * first_id + count > 256, an entry with type outside 0..4, unknown flag bits, a non-finite or negative
+ * color or emission component, ior not finite or <= 0, alpha not in (0, 1], an f0 component not in
+ * [0, 1]; RT_ERR_STATE before rt_init; RT_ERR_HIP for a failed allocation or copy.  Never
+ * RT_ERR_DEVICE. */
+#define RT_MAT_LAMBERTIAN 0
+#define RT_MAT_MIRROR     1
+#define RT_MAT_GLASS      2
+#define RT_MAT_MICROFACET 3
+#define RT_MAT_EMISSIVE   4
+#define RT_MAT_FLAG_FLAT  1u   /* diffuse types: no soil texture */
+typedef struct rt_material {
+    int32_t  type;      /* RT_MAT_* */
+    uint32_t flags;     /* RT_MAT_FLAG_* */
+    float color[3];     /* diffuse types: multiplies the albedo (textured) or is the albedo (flat) */
+    float emission[3];  /* EMISSIVE: radiance of a hit, before the path tracer's clamp at 10 */
+    float ior;          /* GLASS: etaT (the reference's 1.33f) */
+    float alpha;        /* MICROFACET: GGX alpha (0.05f) */
+    float f0[3];        /* MICROFACET: (0.56f, 0.57f, 0.58f) */
+} rt_material;
+int rt_default_material(uint32_t id, rt_material* out);
+int rt_set_materials(rt_context* ctx, uint32_t first_id, uint32_t count, const rt_material* m);
+int rt_get_materials(const rt_context* ctx, uint32_t first_id, uint32_t count, rt_material* out);
+int rt_reset_materials(rt_context* ctx);
+
 /* BASELINE config 2: GenerateRay + RaySceneIntersect for every render pixel with the
  * blue-noise sample of frame_num (pathtrace.cuh:116-130), enqueued asynchronously.
  * with_detail != 0 also stores normals / shading normals / traversal counters. */

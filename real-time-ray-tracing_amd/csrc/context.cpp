@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <fstream>
 #include <sstream>
 
@@ -1180,7 +1181,10 @@ int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* 
     p.count = u->count;
     p.triCount = ctx->mesh.triCount;
     p.capBytes = (uint32_t)ctx->matBytes;
-    p.classes = u->classes;
+    // under a custom material table (rt_set_materials) the class of an id follows its entry's type and
+    // every frame runs the all-classes kernels: the set records every class, replaces and counts nothing
+    const uint32_t classes = ctx->matCustom ? RT_MAT_CLASS_ALL : u->classes;
+    p.classes = classes;
     HIP_TRY(ctx, rtk_launch_mat_set(&p, s));
     HIP_TRY(ctx, hipEventRecord(ctx->matDone, s));
     // the caller's later work on the context stream follows the read of its buffer, and so does every
@@ -1189,8 +1193,121 @@ int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* 
     dst.readValid = dst.specValid = false;
     ctx->matCur = next;
     ctx->dTriMat = dst.ids;
-    ctx->triMatClasses = u->classes;  // the plan of later frames: exactly the declared bits
+    ctx->triMatClasses = classes;  // the plan of later frames: exactly the declared bits
     ctx->matDevice = true;
+    ++ctx->matSerial;
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- the material table
+//
+// What an id means (rt_set_materials).  The host keeps the 256 entries as the caller
+// gave them; the device gets one 64-byte record each (MatRecord), written in place behind the wait for
+// every stream.
+
+int rt_default_material(uint32_t id, rt_material* out) {
+    if (!out || id > 255u) return RT_ERR_ARG;
+    rt_material m = {};
+    // mat_type (shade.h), restated for the host: 0, 2 emissive; 1 glass; 3, 6..9 Lambertian; 4
+    // microfacet; 5 and everything past the ten-entry table mirror
+    m.type = (id == 0u || id == 2u) ? RT_MAT_EMISSIVE
+             : id == 1u             ? RT_MAT_GLASS
+             : id == 4u             ? RT_MAT_MICROFACET
+             : (id == 5u || id >= 10u) ? RT_MAT_MIRROR
+                                       : RT_MAT_LAMBERTIAN;
+    m.flags = 0u;
+    for (int k = 0; k < 3; ++k) {
+        m.color[k] = 1.0f;
+        m.emission[k] = 0.0f;
+    }
+    m.ior = 1.33f;
+    m.alpha = 0.05f;
+    m.f0[0] = 0.56f;
+    m.f0[1] = 0.57f;
+    m.f0[2] = 0.58f;
+    *out = m;
+    return RT_OK;
+}
+
+static const char* material_fault(const rt_material& m) {
+    if (m.type < RT_MAT_LAMBERTIAN || m.type > RT_MAT_EMISSIVE) return "type must be one of RT_MAT_*";
+    if ((m.flags & ~RT_MAT_FLAG_FLAT) != 0u) return "unknown flag bits";
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(m.color[k]) || m.color[k] < 0.0f) return "color must be finite and not negative";
+        if (!std::isfinite(m.emission[k]) || m.emission[k] < 0.0f) return "emission must be finite and not negative";
+    }
+    if (!std::isfinite(m.ior) || !(m.ior > 0.0f)) return "ior must be finite and positive";
+    if (!(m.alpha > 0.0f && m.alpha <= 1.0f)) return "alpha must lie in (0, 1]";
+    for (int k = 0; k < 3; ++k)
+        if (!(m.f0[k] >= 0.0f && m.f0[k] <= 1.0f)) return "f0 must lie in [0, 1]";
+    return nullptr;
+}
+
+static MatRecord material_record(const rt_material& m) {
+    MatRecord r = {};
+    memcpy(r.color, m.color, 12);
+    r.typeFlags = (uint32_t)m.type | (m.flags << 8);
+    memcpy(r.f0, m.f0, 12);
+    r.alpha = m.alpha;
+    memcpy(r.emission, m.emission, 12);
+    r.ior = m.ior;
+    return r;
+}
+
+int rt_set_materials(rt_context* ctx, uint32_t first_id, uint32_t count, const rt_material* m) {
+    if (!ctx || !m) return RT_ERR_ARG;
+    if (count == 0u || (uint64_t)first_id + (uint64_t)count > 256u) {
+        ctx->err = "rt_set_materials: [first_id, first_id + count) must be a non-empty range of the ids 0..255";
+        return RT_ERR_ARG;
+    }
+    for (uint32_t k = 0; k < count; ++k)
+        if (const char* bad = material_fault(m[k])) {
+            ctx->err = "rt_set_materials: entry " + std::to_string(first_id + k) + ": " + bad;
+            return RT_ERR_ARG;
+        }
+    if (!ctx->inited) { ctx->err = "rt_set_materials before rt_init"; return RT_ERR_STATE; }
+    // the kernels in flight read the table, and camera rays traced ahead precede it (spec_matches)
+    if (int rc = sync_streams(ctx, false)) return rc;
+    std::vector<rt_material> next = ctx->matCustom ? ctx->matHost : std::vector<rt_material>();
+    if (next.empty()) {
+        next.resize(256);
+        for (uint32_t id = 0; id < 256u; ++id) (void)rt_default_material(id, &next[id]);
+    }
+    for (uint32_t k = 0; k < count; ++k) next[first_id + k] = m[k];
+    std::vector<MatRecord> recs(256);
+    bool emits = false;
+    for (uint32_t id = 0; id < 256u; ++id) {
+        recs[id] = material_record(next[id]);
+        const rt_material& e = next[id];
+        emits = emits || (e.type == RT_MAT_EMISSIVE && (e.emission[0] > 0.0f || e.emission[1] > 0.0f || e.emission[2] > 0.0f));
+    }
+    if (!ctx->dMatTable) {
+        if (int rc = dalloc(ctx, &ctx->dMatTable, 256 * sizeof(MatRecord))) return rc;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->dMatTable, recs.data(), 256 * sizeof(MatRecord), hipMemcpyHostToDevice));
+    ctx->matHost.swap(next);
+    ctx->matCustom = true;
+    ctx->matEmits = emits;
+    ++ctx->matSerial;
+    return RT_OK;
+}
+
+int rt_get_materials(const rt_context* ctx, uint32_t first_id, uint32_t count, rt_material* out) {
+    if (!ctx || !out) return RT_ERR_ARG;
+    if (count == 0u || (uint64_t)first_id + (uint64_t)count > 256u) return RT_ERR_ARG;
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ctx->matCustom) out[k] = ctx->matHost[first_id + k];
+        else (void)rt_default_material(first_id + k, &out[k]);
+    }
+    return RT_OK;
+}
+
+int rt_reset_materials(rt_context* ctx) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_reset_materials before rt_init"; return RT_ERR_STATE; }
+    if (int rc = sync_streams(ctx, false)) return rc;
+    ctx->matCustom = false;  // the buffer stays allocated for the next set
+    ctx->matEmits = false;
     ++ctx->matSerial;
     return RT_OK;
 }

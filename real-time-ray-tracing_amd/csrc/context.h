@@ -353,6 +353,14 @@ struct rt_context {
     uint32_t* dMatBad = nullptr;        // k_mat_set's count of undeclared ids, zero between sets
     hipEvent_t matSrc = nullptr;        // the context stream's work up to a set without a ready event
     hipEvent_t matDone = nullptr;       // the last device set's end
+    // the material table (rt_set_materials): what an id means.  matCustom false (before the first set,
+    // after rt_reset_materials): the reference's constants, no table reaches a launch.  The setters
+    // write the one device buffer in place behind their wait for every stream; it belongs to the
+    // context and outlives rt_set_mesh*
+    bool matCustom = false;
+    bool matEmits = false;              // an EMISSIVE entry of the custom table has a non-zero emission
+    std::vector<rt_material> matHost;   // [256] the custom table's entries (empty until the first set)
+    MatRecord* dMatTable = nullptr;     // [256], allocated by the first set
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
     // and the setters that change the stream drain it), and on a context without a post stream the

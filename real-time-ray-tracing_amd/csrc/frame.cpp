@@ -759,6 +759,12 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
         p.triMat = m >= 0 ? nullptr : ctx->dTriMat;
         p.ws.glossy = (classes & RT_MAT_CLASS_GLOSSY) != 0u;
         p.ws.microfacet = (classes & RT_MAT_CLASS_MICROFACET) != 0u;
+        // a custom material table (rt_set_materials): an id's class follows its entry, so every class;
+        // the one table-reading variant is the all-classes kernels' on the unsplit plan (pt_bounce_plan
+        // gives it for these two flags), and an emitter makes queue 4 a closest-hit queue
+        p.matTable = ctx->matCustom ? reinterpret_cast<const float4*>(ctx->dMatTable) : nullptr;
+        if (p.matTable) p.ws.glossy = p.ws.microfacet = 1;
+        p.ws.closest4 = p.matTable && ctx->matEmits ? 1 : 0;
     }
     return qs;
 }

@@ -63,7 +63,8 @@ struct HistCamera { float pos[3], left[3], up[3], dir[3]; };  // HistoryCamera (
 //   st2   = beta0.xyz, 0
 // rayD.w bit 0: the entry is a shadow ray (isShadowRay).  Only whether a shadow ray, or any
 // step-4 ray, hits something decides its sample's colour (the path ends there, and a hit never
-// has matType MAT_SKY), so the queue tracer ends those traversals at their first hit.
+// has matType MAT_SKY), so the queue tracer ends those traversals at their first hit.  (The one
+// exception: emitters of a custom material table, PtWorkspace::closest4.)
 constexpr uint32_t kQShadowFlag = 1u;
 
 // Whether the resume of a queue-3 entry can reach the diffuse interaction D1: only a bounce ray
@@ -133,6 +134,9 @@ struct PtWorkspace {
     int glossy;                 // materials can be glossy: steps 1-2 may trace
     int microfacet;             // materials can be the microfacet one (id 4): GGX compiled in
     int chain = 1;              // default materials: trace<3> .. resume<4> as one launch (k_pt_chain)
+    // a custom material table with an emitter: which triangle a step-4 ray hits then decides its sample's
+    // colour, so k_trace_queue<4> finds the closest hit instead of ending at the first
+    int closest4 = 0;
     uint32_t* itersOut = nullptr;  // optional [cap]: traversal iterations per queue entry (rt_trace_rays)
     unsigned long long* q3HostOut = nullptr;  // optional, pinned host memory: {queue 3's length, q3Tag},
     uint32_t q3Tag = 0;                       // stored by k_pt_resolve in one 64-bit store
@@ -206,7 +210,27 @@ struct PathTraceParams {
     // optional [triCountPadded] material id per triangle (SceneMaterial::materialsIdx, kernel.cuh:198-203;
     // rt_set_triangle_materials); null: the reference table, 3 everywhere (update_material)
     const uint8_t* triMat;
+    // optional [256 * kMatRecVecs] the custom material table (rt_set_materials): record `id` is the four
+    // float4 of a MatRecord.  Null: the reference's constants (shade.h), and the launch sequence is the
+    // one of a context without the feature; set: the table-reading kernels (kTab of k_pt_shade0 and
+    // k_pt_resume), always with ws.glossy and ws.microfacet
+    const float4* matTable;
 };
+
+// One entry of the device material table, 64 B: each of its vectors is one aligned 16-byte load of the
+// lane that needs it (the type with the colour at a hit and in D0 / D1, the GGX pair in the microfacet
+// branch, the emission or the index of refraction where a path ends or refracts).
+constexpr int kMatRecVecs = 4;
+struct alignas(16) MatRecord {
+    float color[3];
+    uint32_t typeFlags;  // rt_material::type | flags << 8
+    float f0[3];
+    float alpha;
+    float emission[3];
+    float ior;
+    float pad[4];
+};
+static_assert(sizeof(MatRecord) == 16 * kMatRecVecs, "four 16-byte vectors");
 
 // TemporalSpatialDenoising + PostProcessing + CopyToOutput (denoise.hip)
 struct DenoisePostParams {

@@ -80,6 +80,14 @@ struct PathVars {
     F3 outNormal;
 };
 
+// Vector k of entry `id & 255` of the custom material table (MatRecord, frame_kernels.h): one aligned
+// 16-byte load, indexed per lane.  The buffer holds all 256 records, so every id is in bounds.
+RT_DEV float4 mat_vec(const PathTraceParams& P, int id, int k) { return P.matTable[(id & 255) * kMatRecVecs + k]; }
+
+// kTab: the launch carries a custom material table (rt_set_materials; P.matTable set).  The type,
+// colour, GGX parameters, index of refraction and emission of a hit then come from its entry instead
+// of the reference's constants; instantiated on the all-classes kernels only.
+template <bool kTab = false>
 RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
     // values first, one store each: stores sunk behind a branch became a private array
     // materialsIdx[objectIdx] (traverse.cuh:29-32): P.triMat, or 3 everywhere without a table
@@ -88,7 +96,9 @@ RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
     int tableId = 3;
     if (P.triMat && inRange) tableId = (int)P.triMat[rs.objectIdx];
     const int id = P.materialOverride >= 0 ? P.materialOverride : inRange ? tableId : 6;  // SAFE_LOAD(.., 6)
-    const int type = (id >= 0 && id < 10) ? mat_type(id) : PERFECT_REFLECTION;
+    int type;
+    if constexpr (kTab) type = (int)(__float_as_uint(mat_vec(P, id, 0).w) & 0xFFu);
+    else type = (id >= 0 && id < 10) ? mat_type(id) : PERFECT_REFLECTION;
     rs.matId = rs.hit ? id : 99999;
     rs.matType = rs.hit ? type : MAT_SKY;
     if (rs.isShadowRay) {
@@ -106,6 +116,7 @@ RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
 RT_DEV bool needs_trace(const RayState& rs) { return !(rs.hitLight || !rs.isHitProcessed || rs.isOccluded); }
 
 // ... and what it does with the hit
+template <bool kTab = false>
 RT_DEV void apply_hit(const PathTraceParams& P, RayState& rs, const HitInfo& h) {
     rs.isHitProcessed = false;
     rs.offset = h.offset;
@@ -118,10 +129,11 @@ RT_DEV void apply_hit(const PathTraceParams& P, RayState& rs, const HitInfo& h) 
     rs.hit = h.hit;
     rs.depth = h.t;
     if (rs.hit) rs.rayConeWidth += rs.rayConeSpread * h.t;
-    update_material(P, rs);
+    update_material<kTab>(P, rs);
 }
 
 // GlossySurfaceInteraction (surfaceInteraction.cuh:11-34, bsdf.cuh:130-165); random number rn[0][k]
+template <bool kTab = false>
 RT_DEV void glossy(const PathCtx& c, RayState& rs, int k) {
     if (rs.hitLight || rs.isDiffuse || rs.isOccluded) return;
     rs.isHitProcessed = true;
@@ -130,6 +142,7 @@ RT_DEV void glossy(const PathCtx& c, RayState& rs, int k) {
         rs.orig = rs.pos + rs.offset * rs.normal;
     } else if (rs.matType == FRESNEL_RR) {
         float etaI = 1.0f, etaT = 1.33f;
+        if constexpr (kTab) etaT = mat_vec(c.P, rs.matId, 2).w;  // rt_material::ior
         if (!rs.isRayIntoSurface) { const float t = etaI; etaI = etaT; etaT = t; }
         const float eta = etaI / etaT;
         const float ndr = rs.normalDotRayDir;
@@ -178,7 +191,7 @@ RT_DEV void tri_plane(const PathTraceParams& P, F2 uv, float lod, F3 normal, F3 
 // rn[2*bounce+1].  kMF: the material table can hold the microfacet material (id 4: materialOverride
 // or a triangle's entry, rt_material_classes); without it the GGX branch, whose live values set the
 // kernels' register peak, is not compiled in.
-template <bool kMF>
+template <bool kMF, bool kTab = false>
 RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     if (rs.hitLight || !rs.isDiffuse || rs.isOccluded) return;
     const PathTraceParams& P = c.P;
@@ -188,7 +201,11 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     F3 normal = rs.fakeNormal;
     const F3 surfaceNormal = rs.normal;
     F3 albedo;
-    {
+    // RT_MAT_FLAG_FLAT: the texture block is skipped, the albedo is the entry's colour and the shading
+    // normal stays the hit's interpolated one
+    bool flat = false;
+    if constexpr (kTab) flat = ((__float_as_uint(mat_vec(P, rs.matId, 0).w) >> 8) & RT_MAT_FLAG_FLAT) != 0u;
+    if (!flat) {
         const float lod = rt_log2f_div(rs.rayConeWidth * 0.5f * __builtin_sqrtf(1024.0f * 1024.0f + 1024.0f * 1024.0f));
         const float wx = surfaceNormal.x * surfaceNormal.x, wy = surfaceNormal.y * surfaceNormal.y,
                     wz = surfaceNormal.z * surfaceNormal.z;
@@ -210,6 +227,10 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
         normal = normalize(accN);
         rs.fakeNormal = normal;
     }
+    if constexpr (kTab) {  // the colour: once, behind the three-plane sum (1 is the identity, bit for bit)
+        const float4 m0 = mat_vec(P, rs.matId, 0);
+        albedo = flat ? f3(m0.x, m0.y, m0.z) : albedo * f3(m0.x, m0.y, m0.z);
+    }
     if (bounce == 0) rs.albedo = albedo * (1.0f + fabsf(dot(normal, rs.centerRaydir)));
     float r[4], r2[4];
 #pragma unroll
@@ -230,8 +251,14 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
         sPdf = div_pi(fmx(dot(sDir, normal), kSafeCos));
         lBsdf = sBsdf;  // albedo / kPi
     } else {  // MICROFACET
-        const F3 F0 = mat_F0(rs.matId);
-        const float alpha = mat_alpha(rs.matId), alpha2 = alpha * alpha;
+        F3 F0 = mat_F0(rs.matId);
+        float alpha = mat_alpha(rs.matId);
+        if constexpr (kTab) {
+            const float4 m1 = mat_vec(P, rs.matId, 1);  // rt_material::f0, alpha
+            F0 = f3(m1.x, m1.y, m1.z);
+            alpha = m1.w;
+        }
+        const float alpha2 = alpha * alpha;
         const F3 sn = ggx_normal(F2{r[0], r[1]}, alpha2, normal);
         sDir = normalize(reflect3(rayDir, sn));
         if (dot(sDir, surfaceNormal) < 0.0f) {
@@ -304,10 +331,10 @@ RT_DEV void gbuffer_step0(const PathCtx& c, PathVars& v) {
 // tracer), applied before the loop so that the record is dead by the first interaction.  An
 // intersection at a step >= kDeferFrom is not traced here: the step is returned and the caller
 // queues the ray.  Returns 5 when the path is complete.
-template <int kDeferFrom, bool kMF>
+template <int kDeferFrom, bool kMF, bool kTab = false>
 RT_DEV int run_path(PathCtx& c, PathVars& v, int k0, const HitInfo* hit, const SceneView& sc, uint2* stk) {
     RayState& rs = v.rs;
-    if (hit) apply_hit(c.P, rs, *hit);
+    if (hit) apply_hit<kTab>(c.P, rs, *hit);
 #pragma unroll 1
     for (int k = k0; k < 5; ++k) {
         if ((k != k0 || !hit) && needs_trace(rs)) {
@@ -317,15 +344,15 @@ RT_DEV int run_path(PathCtx& c, PathVars& v, int k0, const HitInfo* hit, const S
             intersect(sc, rs.orig, rs.dir, stk, 256, h);
             c.visits += h.visits;
             c.tests += h.tests;
-            apply_hit(c.P, rs, h);
+            apply_hit<kTab>(c.P, rs, h);
         }
         if (k == 0) gbuffer_step0(c, v);
         if (k == 4) break;
-        glossy(c, rs, k);
+        glossy<kTab>(c, rs, k);
         if (k >= 2) {
             const bool first = k == 2;
             F3 beta = f3(1.0f);
-            diffuse<kMF>(c, first ? 0 : 1, rs, beta);
+            diffuse<kMF, kTab>(c, first ? 0 : 1, rs, beta);
             if (first) {
                 v.beta1 = beta;
                 v.outNormal = rs.fakeNormal;
@@ -357,10 +384,19 @@ RT_DEV int run_shade0_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
 }
 
 // end of PathTrace (pathtrace.cuh:103-128): the sample's demodulated colour
+// kTab: a path that ends on an emissive hit carries its entry's emission (emitters are not sampled
+// as lights: only a camera or bounce ray that lands on one sees it)
+template <bool kTab = false>
 RT_DEV F3 finish(const PathCtx& c, const PathVars& v) {
     const RayState& rs = v.rs;
     F3 L0 = f3(0.0f);
     if (rs.hitLight && !rs.isOccluded && rs.matType == MAT_SKY) L0 = env_light(c.P, c.sunDir, rs.dir);
+    if constexpr (kTab) {
+        if (rs.hitLight && !rs.isOccluded && rs.matType == EMISSIVE) {
+            const float4 m2 = mat_vec(c.P, rs.matId, 2);  // rt_material::emission
+            L0 = f3(m2.x, m2.y, m2.z);
+        }
+    }
     F3 L2 = L0 * v.beta0 * v.beta1;
     if (isnan3(L2)) L2 = f3(0.0f);
     L2 = f3(clampf(L2.x, 0.0f, 10.0f), clampf(L2.y, 0.0f, 10.0f), clampf(L2.z, 0.0f, 10.0f));
@@ -690,7 +726,10 @@ RT_DEV uint32_t claim_next(ShadeClaim& c, uint32_t* counters, uint32_t& slot) {
 // glass the sample runs run_shade0_diffuse, so the one-round kernel fits 168 VGPRs without
 // scratch: 3 waves per SIMD instead of 2 (229 VGPRs through the step loop; serial 0.212 ->
 // 0.190 ms, synchronous draw 1.089 -> 1.069 ms, profiles/r05_ab/shade0_straight/).
-template <bool kGlossy, bool kMF, bool kOneRound>
+//
+// kTab: the launch carries a custom material table (rt_set_materials): the all-classes kernel reading
+// the table.  A trailing, defaulted parameter: the other instantiations compile exactly as before.
+template <bool kGlossy, bool kMF, bool kOneRound, bool kTab = false>
 #ifndef RTX_SHADE_WAVES  // A/B builds only (tools/abl_build.sh): waves per SIMD of the default-material variant
 #define RTX_SHADE_WAVES 3
 #endif
@@ -753,7 +792,8 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
                 HitInfo h;
                 finalize_hit(sc, v.rs.orig, v.rs.dir, hr.x, (int)__float_as_uint(hr.y), hr.z, hr.w, P.ws.hit0Err[q],
                              h);
-                if constexpr (kGlossy) kd = run_path<3, kMF>(c, v, 0, &h, sc, stk + tid);
+                static_assert(!kTab || kGlossy, "the table variant is the all-classes kernel's");
+                if constexpr (kGlossy) kd = run_path<3, kMF, kTab>(c, v, 0, &h, sc, stk + tid);
                 else kd = run_shade0_diffuse<kMF>(c, v, h);
                 if (kd < 3) {  // cannot happen without mirror/glass materials: flag it, finish the sample
                     atomicAdd(&P.ws.counters[kCntError], 1u);
@@ -776,7 +816,7 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
                     enqueue(kd == 3 ? P.ws.q3 : P.ws.q4, kd == 3 ? slot3 : slot4, v, p, (uint32_t)s);
                     outL.w = 1.0f;
                 } else {
-                    const F3 Ls = finish(c, v);
+                    const F3 Ls = finish<kTab>(c, v);
                     outL = make_float4(Ls.x, Ls.y, Ls.z, 0.0f);
                 }
             }
@@ -902,12 +942,12 @@ __global__ __launch_bounds__(256) void k_pt_geom_motion(PathTraceParams P) {
 // run_path<0, kMF>(c, v, kStep, &hit, ..) in straight line where no glossy interaction can run:
 // step 4 (it ends the path) for any table, step 3 without mirror or glass (as run_shade0_diffuse:
 // G3 returns at once, so step 3 is D1 and step 4 traces exactly when D1 produced a ray)
-template <int kStep, bool kMF>
+template <int kStep, bool kMF, bool kTab = false>
 RT_DEV int resume_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
-    apply_hit(c.P, v.rs, hit);
+    apply_hit<kTab>(c.P, v.rs, hit);
     if (kStep == 4) return 5;
     F3 beta = f3(1.0f);
-    diffuse<kMF>(c, 1, v.rs, beta);
+    diffuse<kMF, kTab>(c, 1, v.rs, beta);
     v.beta0 = beta;
     return needs_trace(v.rs) ? 4 : 5;
 }
@@ -948,19 +988,20 @@ RT_DEV void reload_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint
 // Entry i of queue kStep (3 or 4): reloads the sample's state, applies the hit the tracer found
 // and runs the rest of its sequence.  Returns 4 when the I4 ray must be traced (kStep == 3 only),
 // else 5 (the sample is complete).  kGlossy: the material table holds mirror or glass.
-template <int kStep, bool kMF, bool kGlossy>
+template <int kStep, bool kMF, bool kGlossy, bool kTab = false>
 RT_DEV int resume_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
                         PathVars& v, uint32_t& p, uint32_t& s) {
     HitInfo h;
     reload_entry(c, q, sc, i, hr, herr, v, p, s, h);
-    if constexpr (kGlossy && kStep == 3) return run_path<0, kMF>(c, v, kStep, &h, sc, nullptr);
-    else return resume_diffuse<kStep, kMF>(c, v, h);
+    if constexpr (kGlossy && kStep == 3) return run_path<0, kMF, kTab>(c, v, kStep, &h, sc, nullptr);
+    else return resume_diffuse<kStep, kMF, kTab>(c, v, h);
 }
 
 // a completed sample of a queue entry: its radiance goes to the late-resolve slot
+template <bool kTab = false>
 RT_DEV void store_path_L(const PathCtx& c, const PathVars& v, uint32_t p, uint32_t s) {
     const PathTraceParams& P = c.P;
-    const F3 Ls = finish(c, v);
+    const F3 Ls = finish<kTab>(c, v);
     const uint32_t pl = local_row(P.y0, P.nStrips, p / P.width) * P.width + p % P.width;
     P.ws.pathL[(size_t)pl * P.spp + s] = make_float4(Ls.x, Ls.y, Ls.z, 0.0f);
 }
@@ -970,6 +1011,7 @@ RT_DEV void store_path_L(const PathCtx& c, const PathVars& v, uint32_t p, uint32
 // Called by every lane of the wave (wave_append); an idle lane passes active = false, kd = 5.
 // Adds the lane's counts to the caller's rays and rsD (the latter in detail launches only) and
 // returns its queue-4 slot.
+template <bool kTab = false>
 RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd, uint32_t p, uint32_t s, uint32_t& rays,
                              uint32_t& rsD) {
     const PathTraceParams& P = c.P;
@@ -979,7 +1021,7 @@ RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd,
             ++c.rays;
             enqueue(P.ws.q4, slot, v, p, s);
         } else {
-            store_path_L(c, v, p, s);
+            store_path_L<kTab>(c, v, p, s);
         }
         if (P.raysOut && c.rays) atomicAdd(&P.raysOut[p], c.rays);
         if (P.statsOut) {
@@ -995,7 +1037,7 @@ RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd,
 // One workgroup of a resume kernel: the samples of queue kStep (3 or 4) once k_trace_queue has
 // written their hits.  kListed (queue 3, no mirror or glass): not the queue in order but its
 // entries on the shading list ws.shade3, one listed entry per lane.
-template <int kStep, bool kMF, bool kGlossy, bool kListed>
+template <int kStep, bool kMF, bool kGlossy, bool kListed, bool kTab = false>
 RT_DEV void resume_queue(const PathTraceParams& P) {
     static_assert(!kListed || (kStep == 3 && !kGlossy), "the shading list is queue 3's, kept without glossy tables");
     __shared__ uint32_t sob[256];
@@ -1027,18 +1069,21 @@ RT_DEV void resume_queue(const PathTraceParams& P) {
         uint32_t p = 0, s = 0;
         if (active) {
             const uint32_t i = kListed ? P.ws.shade3[li] : li;
-            kd = resume_entry<kStep, kMF, kGlossy>(c, q, sc, i, hitRec[i], hitErr[i], v, p, s);
+            kd = resume_entry<kStep, kMF, kGlossy, kTab>(c, q, sc, i, hitRec[i], hitErr[i], v, p, s);
         }
-        finish_entry(c, v, active, kd, p, s, rays, rsD);
+        finish_entry<kTab>(c, v, active, kd, p, s, rays, rsD);
     }
     if (kStep == 3 && P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays);
 }
 
 // Queue kStep taken in order: queue 4 always, queue 3 when it keeps no shading list.
-template <int kStep, bool kMF, bool kGlossy>
+// kTab: under a custom material table (rt_set_materials), the all-classes body reading the table.  Step 4
+// shades nothing; its variant differs in finish() only (the emission of the entry the path ended on).
+template <int kStep, bool kMF, bool kGlossy, bool kTab = false>
 __global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_resume(PathTraceParams P) {
-    resume_queue<kStep, kMF, kGlossy, false>(P);
+    static_assert(!kTab || kStep == 4 || (kMF && kGlossy), "the table variant is the all-classes kernel's");
+    resume_queue<kStep, kMF, kGlossy, false, kTab>(P);
 }
 
 // The split resume<3> (ws.shade3 set; default materials or the microfacet one): of the queue-3
@@ -1352,9 +1397,12 @@ dim3 shade_grid(const PathTraceParams* p, K kernel, int& cached) {
 
 template <bool kOneRound>
 void launch_shade_rounds(const PathTraceParams* p, hipStream_t stream) {
-    static int occ[4];
+    static int occ[5];
     const dim3 pb(256);
-    if (p->ws.glossy && p->ws.microfacet) {  // a triangle table with both classes (rt_set_triangle_materials)
+    if (p->matTable) {  // a custom material table (rt_set_materials): every class, parameters from the table
+        auto k = k_pt_shade0<true, true, kOneRound, true>;
+        hipLaunchKernelGGL(k, shade_grid(p, k, occ[4]), pb, 0, stream, *p);
+    } else if (p->ws.glossy && p->ws.microfacet) {  // a triangle table with both classes (rt_set_triangle_materials)
         auto k = k_pt_shade0<true, true, kOneRound>;
         hipLaunchKernelGGL(k, shade_grid(p, k, occ[3]), pb, 0, stream, *p);
     } else if (p->ws.glossy) {
@@ -1438,6 +1486,8 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
     }
     if (e != hipSuccess) return e;
     const PtBouncePlan plan = pt_bounce_plan(p->ws);
+    // a custom table has the unsplit kernels only: the host sets both classes with it (fill_pt_params)
+    if (p->matTable && plan != PtBouncePlan::unsplit) return hipErrorInvalidValue;
     if (plan == PtBouncePlan::chain) {
         // kernel 2 = the fused bounce chain (trace<3> .. resume<4>); slots 3-5 stay empty, so the
         // hook's kernel numbers and the per-kernel timing slots keep their meaning
@@ -1462,12 +1512,15 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
                 (void)kernel(p->ws.microfacet ? k_pt_resume3_shade<true> : k_pt_resume3_shade<false>, pg, stream);
                 return forked ? hipSuccess : kernel(k_pt_resume3_lean, pg, stream);
             }
+            if (p->matTable) return kernel(k_pt_resume<3, true, true, true>, pg, stream);
             return kernel(p->ws.glossy       ? (p->ws.microfacet ? k_pt_resume<3, true, true> : k_pt_resume<3, false, true>)
                           : p->ws.microfacet ? k_pt_resume<3, true, false>
                                              : k_pt_resume<3, false, false>, pg, stream);
         });
         if (e == hipSuccess) e = stage([&] { return rtk_launch_trace_queue(p, 4, stream); });
-        if (e == hipSuccess) e = stage([&] { return kernel(k_pt_resume<4, false, false>, pg, stream); });  // step 4 shades nothing
+        // step 4 shades nothing; under a custom table it reads the emission of the entry a path ended on
+        if (e == hipSuccess)
+            e = stage([&] { return kernel(p->matTable ? k_pt_resume<4, false, false, true> : k_pt_resume<4, false, false>, pg, stream); });
         if (e == hipSuccess && forked) e = hipStreamWaitEvent(stream, fork->done, 0);  // its pathL stores
         if (e != hipSuccess) return e;
     }

@@ -45,7 +45,9 @@ RT_DEV void flush_shade_list(const PathTraceParams& P, uint32_t* shl, uint32_t n
 }
 
 // kStats: the launch keeps per-pixel statistics (P.statsOut), so the traversal counts visits and tests
-template <int kStep, bool kStats>
+// kClosest (queue 4 under a custom material table with an emitter, PtWorkspace::closest4): a bounce
+// ray's traversal runs to its closest hit, since which triangle it lands on decides the sample's colour
+template <int kStep, bool kStats, bool kClosest = false>
 __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) {
     __shared__ uint2 stk[17 * kTraceBlock];  // 16 entries + the dead slot trav_step stores above the top
     __shared__ uint32_t shadeList[kStep == 3 ? kTraceBlock : 1];  // per wave: 64 pending shading-list entries
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
                     trav_init(s, sc.root);
                     rec = trav_first_rec(sc);
                     active = true;
-                    occlusion = kStep == 4 || (__float_as_uint(d.w) & kQShadowFlag) != 0u;
+                    occlusion = (kStep == 4 && !kClosest) || (__float_as_uint(d.w) & kQShadowFlag) != 0u;
                 } else if (none) {
                     exhausted = true;
                 }
@@ -187,6 +189,7 @@ extern "C" hipError_t rtk_launch_trace_queue(const PathTraceParams* p, int step,
     const bool stats = p->statsOut != nullptr;
     void (*k)(PathTraceParams) = step == 3 ? (stats ? k_trace_queue<3, true> : k_trace_queue<3, false>)
                                            : (stats ? k_trace_queue<4, true> : k_trace_queue<4, false>);
+    if (step == 4 && p->ws.closest4) k = stats ? k_trace_queue<4, true, true> : k_trace_queue<4, false, true>;
     hipLaunchKernelGGL(k, grid, dim3(kTraceBlock), 0, stream, *p);
     return hipGetLastError();
 }

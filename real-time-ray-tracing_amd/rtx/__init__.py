@@ -114,6 +114,24 @@ class MaterialUpdate(C.Structure):
                 ("ready_event", C.c_void_p)]
 
 
+class Material(C.Structure):
+    """rt_material: one entry of the material table (rt_set_materials)."""
+    _fields_ = [("type", C.c_int32), ("flags", C.c_uint32), ("color", C.c_float * 3), ("emission", C.c_float * 3),
+                ("ior", C.c_float), ("alpha", C.c_float), ("f0", C.c_float * 3)]
+
+    def __eq__(self, other):
+        return isinstance(other, Material) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "Material(type=%d, flags=%d, color=%s, emission=%s, ior=%r, alpha=%r, f0=%s)" % (
+            self.type, self.flags, list(self.color), list(self.emission), self.ior, self.alpha, list(self.f0))
+
+
+MAT_LAMBERTIAN, MAT_MIRROR, MAT_GLASS, MAT_MICROFACET, MAT_EMISSIVE = range(5)  # RT_MAT_*
+MAT_FLAG_FLAT = 1  # RT_MAT_FLAG_FLAT
+
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
 
@@ -186,6 +204,10 @@ SIGNATURES = {
     "rt_material_classes": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rt_set_triangle_materials_device": (C.c_int, [C.c_void_p, C.POINTER(MaterialUpdate)]),
     "rt_material_class_rule": (C.c_uint32, [C.c_uint32]),
+    "rt_default_material": (C.c_int, [C.c_uint32, C.POINTER(Material)]),
+    "rt_set_materials": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material)]),
+    "rt_get_materials": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material)]),
+    "rt_reset_materials": (C.c_int, [C.c_void_p]),
 }
 MAT_CLASS_GLOSSY, MAT_CLASS_MICROFACET = 1, 2  # RT_MAT_CLASS_*
 MAT_CLASS_ALL = MAT_CLASS_GLOSSY | MAT_CLASS_MICROFACET
@@ -484,6 +506,31 @@ class RayTracer:
         """Back to the reference's table, material 3 for every triangle."""
         self._check(self.lib.rt_reset_triangle_materials(self.h), "rt_reset_triangle_materials")
 
+    # ---- the material table (rt_set_materials, include/rtx_amd.h)
+    def set_materials(self, first_id: int, materials):
+        """Replace entries [first_id, first_id + len(materials)) of the material table (a sequence of
+        Material); the other entries stay as they were.  Takes effect for every path trace enqueued
+        after it."""
+        mats = list(materials)
+        if not all(isinstance(m, Material) for m in mats):
+            raise ValueError("set_materials: materials must be rtx.Material instances")
+        if not 0 <= int(first_id) <= 0xFFFFFFFF:
+            raise ValueError("set_materials: first_id must fit 32 bits")
+        arr = (Material * max(len(mats), 1))(*mats)
+        self._check(self.lib.rt_set_materials(self.h, int(first_id), len(mats), arr), "rt_set_materials")
+
+    def get_materials(self, first_id: int = 0, count: int = 256):
+        """Entries [first_id, first_id + count) as a list of Material: what was set, or the defaults."""
+        if not 0 <= int(first_id) <= 0xFFFFFFFF or not 0 <= int(count) <= 0xFFFFFFFF:
+            raise ValueError("get_materials: first_id and count must fit 32 bits")
+        arr = (Material * max(int(count), 1))()
+        self._check(self.lib.rt_get_materials(self.h, int(first_id), int(count), arr), "rt_get_materials")
+        return [Material.from_buffer_copy(arr[k]) for k in range(int(count))]
+
+    def reset_materials(self):
+        """Back to the reference's constants: no custom table."""
+        self._check(self.lib.rt_reset_materials(self.h), "rt_reset_materials")
+
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")
 
@@ -666,6 +713,17 @@ def material_classes(ids) -> int:
     if rc != RT_OK:
         raise RtError("rt_material_classes: %s" % ERRORS.get(rc, rc))
     return c.value
+
+
+def default_material(id: int) -> Material:
+    """rt_default_material: the reference's meaning of material id 0..255.  Host only."""
+    if not 0 <= int(id) <= 0xFFFFFFFF:
+        raise ValueError("default_material: id must fit 32 bits")
+    m = Material()
+    rc = load_library().rt_default_material(int(id), C.byref(m))
+    if rc != RT_OK:
+        raise RtError("rt_default_material: %s" % ERRORS.get(rc, rc))
+    return m
 
 
 def mesh_adjacency(indices_padded, nv: int):

@@ -27,7 +27,10 @@ Writes profiles/materials.json.
 With --device-sets: the table re-set ahead of every frame through rt_set_triangle_materials_device,
 through the host setter, and not at all (device_sets below); writes profiles/materials_device.json.
 
-Usage: python tools/material_probe.py [--device-sets] [--frames 100] [--repeats 5] [--out PATH]"""
+With --material-table: the cost of the table-reading kernel variant of rt_set_materials
+(material_table below); writes profiles/material_table.json.
+
+Usage: python tools/material_probe.py [--device-sets | --material-table] [--frames 100] [--repeats 5] [--out PATH]"""
 import argparse
 import json
 import os
@@ -143,6 +146,93 @@ def device_sets(a):
     print(json.dumps(res))
 
 
+def material_table(a):
+    """--material-table: what the table-reading kernel variant costs (rt_set_materials, DESIGN.md
+    §4.1.4): pipelined 1080p 4-spp frames of the terrain under hashed(MIX8), in ONE context, timed in
+    turn --repeats times (medians of ms per frame):
+
+      mix8        no custom table: the all-classes kernels on the reference's constants
+      mix8_table  the same ids with the defaults passed through rt_set_materials: the same pixels from
+                  the table-reading variant
+      mix8_again  no custom table again: the control
+
+    and per-kernel times of marked frames of the first two.  Writes profiles/material_table.json."""
+    import torch
+
+    import rtx
+    from rtx.frames import FramePipeline
+
+    w, h, spp = 1920, 1080, 4
+    dev = torch.device("cuda", 0)
+    prev = torch.cuda.current_stream(0)
+    names = ("mix8", "mix8_table", "mix8_again")
+    rt = rtx.RayTracer(w, h, rtx.write_config(os.path.join(tempfile.mkdtemp(), "m.toml"), w, h, spp=spp)).init()
+    try:
+        rt.set_delta_time(16.667)
+        cam = rt.camera
+        cam.pos[:] = TERRAIN_CAM["pos"]
+        cam.yaw, cam.pitch = TERRAIN_CAM["yaw"], TERRAIN_CAM["pitch"]
+        rt.camera = cam
+        rt.set_triangle_materials(hashed(int(rt.info().triCount), MIX8))
+        defaults = [rtx.default_material(i) for i in range(256)]
+        fp = FramePipeline(rt, dev, pipelined=True)
+        state = dict(f=0)
+
+        def use(name):  # both calls are setters: they drain the pipeline first
+            if name == "mix8_table":
+                rt.set_materials(0, defaults)
+            else:
+                rt.reset_materials()
+
+        def run(n):
+            for _ in range(n):
+                state["f"] += 1
+                fp.frame(state["f"])
+            fp.finish()
+
+        series = {name: [] for name in names}
+        for _ in range(a.repeats):
+            for name in names:
+                use(name)
+                run(a.warmup)
+                t0 = time.perf_counter()
+                run(a.frames)
+                series[name].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        rows = {}
+        for name in names:
+            use(name)
+            # the blue-noise sequence repeats with the frame index: every marked series starts at the same
+            # phase of it, so that the queue lengths of the last frame compare (equal: the same paths)
+            run((-state["f"]) % 256)
+            run(a.warmup)
+            rt.frame_marks_begin(a.marked)
+            run(a.marked)
+            ms, n = rt.frame_marks_read()
+            q = rt.download("PT_QUEUE", np.uint32)
+            rows[name] = dict(ms_per_frame=float(np.median(series[name])), series_ms=series[name],
+                              last_chain=int(rt.info().lastChain), queue3_entries=int(q[0]), queue4_entries=int(q[1]),
+                              internal_errors=int(q[10]), marked_frames=n,
+                              kernel_ms={k: round(v, 4) for k, v in ms.items()})
+    finally:
+        rt.cleanup()
+        torch.cuda.set_stream(prev)
+    res = dict(device=torch.cuda.get_device_name(0),
+               config="%dx%d, %d spp, terrain camera %r, pipelined FramePipeline, LBVH rebuild every frame, ids hashed(MIX8)"
+                      % (w, h, spp, TERRAIN_CAM),
+               method="one context, the material table set / reset between series; the three timed in turn %d times, %d "
+                      "frames each after %d warm-up frames; ms_per_frame is the median of the series; kernel_ms from %d "
+                      "frames bracketed by events" % (a.repeats, a.frames, a.warmup, a.marked),
+               tables=rows,
+               same_queue_lengths=len({(r["queue3_entries"], r["queue4_entries"]) for r in rows.values()}) == 1,
+               table_cost_ms=rows["mix8_table"]["ms_per_frame"] - rows["mix8"]["ms_per_frame"],
+               control_ms=rows["mix8_again"]["ms_per_frame"] - rows["mix8"]["ms_per_frame"])
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "material_table.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "materials.json")
 
 
@@ -154,10 +244,15 @@ def main():
     ap.add_argument("--marked", type=int, default=20, help="frames whose kernels are bracketed by events")
     ap.add_argument("--device-sets", action="store_true",
                     help="time the table re-set every frame: device call, host setter, no set (profiles/materials_device.json)")
+    ap.add_argument("--material-table", action="store_true",
+                    help="time the table-reading kernel variant against the same ids without a custom table "
+                         "(profiles/material_table.json)")
     ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
     if a.device_sets:
         return device_sets(a)
+    if a.material_table:
+        return material_table(a)
     import torch
 
     import rtx
