@@ -200,6 +200,70 @@ int rt_save_image(rt_context* ctx, const char* path, int kind);
 #define RT_TEX_SOIL_HEIGHT 2
 int rt_upload_texture(rt_context* ctx, int which, const uint16_t* texels, int width, int height, int channels);
 
+/* Texture sets: per-material atlases.  A texture set is one pair of 1024 x 1024,
+ * 11-level ushort4 mip chains (albedo/AO and normal/roughness).  [scene] textureSets = N (absent or 0:
+ * 1; at most RT_TEXTURE_SETS_MAX, about 22.4 MB each) makes the context hold N of them.  An unparsable
+ * or negative value: RT_ERR_IO from rt_create; N > 16: RT_ERR_ARG from rt_init, before any device call.
+ * Set 0 is the soil atlas: rt_upload_texture and RT_ARR_TEX_* mean set 0.  rt_init fills sets 1..N-1
+ * with a copy of set 0, so a set nobody uploaded to renders exactly like set 0.  The height map stays
+ * single (shading does not read it).
+ *
+ * rt_upload_texture_set is rt_upload_texture for any set: synchronous, behind a wait for the renderer's
+ * streams, mips built on the device; `which` is the albedo or the normal map (RT_TEX_SOIL_HEIGHT with
+ * set > 0 is RT_ERR_ARG; with set 0 it is rt_upload_texture's height upload).
+ *
+ * rt_upload_texture_set_device is the stream-ordered counterpart, in the family of
+ * rt_update_vertices_device, rt_set_mesh_device and rt_set_triangle_materials_device: the host is never
+ * synchronised and no stream is drained.  `texels` is device memory, 1024 x 1024 x 4 channels of
+ * `format`, read after ready_event (NULL: after everything enqueued on the context stream so far); work
+ * enqueued on the context stream after the call follows that read.  The write of level 0 and the mip
+ * generation run behind every path trace enqueued before the call, on whichever renderer stream: those
+ * path traces, pipelined frames in flight included, keep the old texels; every path trace enqueued
+ * after the call waits for the upload and sees the new chain.  What a synchronous draw traced ahead is
+ * stale and the next draw traces it again.
+ *
+ * Both calls, checked in this order, and on an error nothing changes: RT_ERR_ARG for NULL ctx, u or
+ * texels, an unknown `which` or format, a misaligned (4 B) device pointer, a wrong size or channel
+ * count; RT_ERR_STATE before rt_init; RT_ERR_ARG for set >= the context's texture sets; RT_ERR_HIP for
+ * a failed launch.  Never RT_ERR_DEVICE. */
+#define RT_TEXTURE_SETS_MAX 16
+int rt_get_texture_sets(const rt_context* ctx, uint32_t* count);
+int rt_upload_texture_set(rt_context* ctx, uint32_t set, int which, const uint16_t* texels, int width, int height,
+                          int channels);
+
+#define RT_TEX_FORMAT_U16 0   /* ushort4 rows, as rt_upload_texture */
+#define RT_TEX_FORMAT_U8  1   /* uchar4 rows; each channel becomes v * 257 (255 -> 65535) */
+typedef struct rt_texture_upload {
+    const void* texels;   /* device memory, 1024 x 1024 x 4 channels, 4-byte aligned */
+    uint32_t set;
+    int32_t which;        /* RT_TEX_SOIL_ALBEDO_AO or RT_TEX_SOIL_NORMAL_ROUGHNESS */
+    uint32_t format;      /* RT_TEX_FORMAT_* */
+    void* ready_event;    /* hipEvent_t or NULL, as in rt_update_vertices_device */
+} rt_texture_upload;
+int rt_upload_texture_set_device(rt_context* ctx, const rt_texture_upload* u);
+
+/* Which texture set a material id samples: a table of its own beside the material table (rt_material is
+ * unchanged), 256 bytes, all 0 by default.  A textured diffuse hit (Lambertian or microfacet, not
+ * RT_MAT_FLAG_FLAT), reached by a camera ray or through bounces, samples both maps of the set bound to
+ * its material id; flat entries, glass, mirrors and emitters ignore the binding; [render]
+ * materialOverride chooses the id, whose binding then applies.  The binding belongs to the context: it
+ * survives rt_set_mesh*, rt_set_materials and rt_reset_materials, and only rt_reset_material_textures
+ * clears it; rt_get_materials is unaffected.
+ *
+ * A binding that is all zeros is no binding: the path trace launches exactly the kernels it launches
+ * without these calls.  With any non-zero entry every frame runs the table-reading kernels of
+ * rt_set_materials on the unsplit plan (without a custom table, over rt_default_material's entries,
+ * under which they are the identity bit for bit).
+ *
+ * The setters behave like rt_set_materials: they wait for the renderer's streams, drop what a
+ * synchronous draw traced ahead and take effect for every path trace enqueued afterwards; they are not
+ * stream-ordered.  Every rank of a multi-GPU run calls with the same data.  On an error nothing changes.
+ * Checked in this order: RT_ERR_ARG for NULL ctx, sets or out, count == 0, first_id + count > 256;
+ * RT_ERR_STATE before rt_init; RT_ERR_ARG for an entry >= the context's texture sets. */
+int rt_set_material_textures(rt_context* ctx, uint32_t first_id, uint32_t count, const uint8_t* sets);
+int rt_get_material_textures(const rt_context* ctx, uint32_t first_id, uint32_t count, uint8_t* sets);
+int rt_reset_material_textures(rt_context* ctx);
+
 /* Scene input (host only, no device needed): Perlin::noise3D (perlin.h:50-78) with the reference
  * permutation, the source of the procedural terrain's voxel heights (Chunk::Generate,
  * terrain.cpp:5-45), at n points (xyz triples). */
@@ -760,6 +824,9 @@ enum rt_array_name {
                                     the device census after rt_set_triangle_materials_device, the host's after
                                     rt_set_triangle_materials, triCount at id 3 without a table */
 };
+/* RT_ARR_TEX_ALBEDO_AO and RT_ARR_TEX_NORMAL_ROUGHNESS OR-ed with RT_ARR_TEX_SET(k) name the chain of
+ * texture set k (k = 0 is the plain name); a k past the context's sets is RT_ERR_ARG (rt_array_bytes: 0). */
+#define RT_ARR_TEX_SET(k) ((k) << 8)
 int rt_download(const rt_context* ctx, int what, void* dst, size_t bytes);
 
 /* Batch ray query: the reference's RaySceneIntersect traversal (traverse.cuh:107-253, the

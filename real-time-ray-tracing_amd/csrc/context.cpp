@@ -360,6 +360,16 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
         }
         (key[3] == 'T' ? ctx->maxTriangles : ctx->maxVertices) = (uint32_t)n;
     }
+    if (const rttoml::Value* v = rttoml::find(doc, "scene", "textureSets")) {  // a count, 0 = 1; the limit is rt_init's
+        char* end = nullptr;
+        const long long n = v->isArray || v->isString || v->raw.empty() ? -1 : strtoll(v->raw.c_str(), &end, 10);
+        if (n < 0 || n > 0x7FFFFFFFll || !end || *end != '\0') {
+            g_createError = "config parse error: [scene] textureSets must be a count";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->textureSets = (int)n;
+    }
     ctx->spp = rttoml::find_or_int(doc, "render", "spp", 1);
     ctx->bvhThreads = rttoml::find_or_int(doc, "render", "bvhThreads", 0);  // LBVH workgroup shape (A/B, tests)
     ctx->device = rttoml::find_or_int(doc, "render", "device", -1);
@@ -440,6 +450,11 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
 int rt_init(rt_context* ctx) {
     if (!ctx) return RT_ERR_ARG;
     if (ctx->inited) { ctx->err = "rt_init called twice"; return RT_ERR_STATE; }
+    if (ctx->textureSets > RT_TEXTURE_SETS_MAX) {
+        ctx->err = "[scene] textureSets out of range: at most " + std::to_string(RT_TEXTURE_SETS_MAX);
+        return RT_ERR_ARG;
+    }
+    ctx->texSets = ctx->textureSets > 0 ? (uint32_t)ctx->textureSets : 1u;
     // ---- scene (init.cu:78-130), built and checked on the host before any device call, so a bad
     // input is reported as such on any machine
     std::string err;
@@ -607,7 +622,7 @@ void rt_destroy(rt_context* ctx) {
     for (const rt_context::MatTable& t : ctx->matPool)
         for (hipEvent_t e : {t.read, t.specRead})
             if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->matSrc, ctx->matDone})
+    for (hipEvent_t e : {ctx->matSrc, ctx->matDone, ctx->texSide, ctx->texLean, ctx->texDone})
         if (e) (void)hipEventDestroy(e);
     if (ctx->sideStream) (void)hipStreamDestroy(ctx->sideStream);
     if (ctx->leanStream) (void)hipStreamDestroy(ctx->leanStream);
@@ -1254,6 +1269,24 @@ static MatRecord material_record(const rt_material& m) {
     return r;
 }
 
+// The device table from the entries (null: rt_default_material's) and the texture-set binding, whose set
+// index rides in bits 16..23 of typeFlags.  Behind the caller's wait for every stream, in place.
+static int write_mat_table(rt_context* ctx, const std::vector<rt_material>* entries, const uint8_t* tex) {
+    std::vector<MatRecord> recs(256);
+    for (uint32_t id = 0; id < 256u; ++id) {
+        rt_material m;
+        if (entries) m = (*entries)[id];
+        else (void)rt_default_material(id, &m);
+        recs[id] = material_record(m);
+        recs[id].typeFlags |= (uint32_t)tex[id] << 16;
+    }
+    if (!ctx->dMatTable) {
+        if (int rc = dalloc(ctx, &ctx->dMatTable, 256 * sizeof(MatRecord))) return rc;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->dMatTable, recs.data(), 256 * sizeof(MatRecord), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
 int rt_set_materials(rt_context* ctx, uint32_t first_id, uint32_t count, const rt_material* m) {
     if (!ctx || !m) return RT_ERR_ARG;
     if (count == 0u || (uint64_t)first_id + (uint64_t)count > 256u) {
@@ -1274,17 +1307,12 @@ int rt_set_materials(rt_context* ctx, uint32_t first_id, uint32_t count, const r
         for (uint32_t id = 0; id < 256u; ++id) (void)rt_default_material(id, &next[id]);
     }
     for (uint32_t k = 0; k < count; ++k) next[first_id + k] = m[k];
-    std::vector<MatRecord> recs(256);
     bool emits = false;
     for (uint32_t id = 0; id < 256u; ++id) {
-        recs[id] = material_record(next[id]);
         const rt_material& e = next[id];
         emits = emits || (e.type == RT_MAT_EMISSIVE && (e.emission[0] > 0.0f || e.emission[1] > 0.0f || e.emission[2] > 0.0f));
     }
-    if (!ctx->dMatTable) {
-        if (int rc = dalloc(ctx, &ctx->dMatTable, 256 * sizeof(MatRecord))) return rc;
-    }
-    HIP_TRY(ctx, hipMemcpy(ctx->dMatTable, recs.data(), 256 * sizeof(MatRecord), hipMemcpyHostToDevice));
+    if (int rc = write_mat_table(ctx, &next, ctx->matTex)) return rc;
     ctx->matHost.swap(next);
     ctx->matCustom = true;
     ctx->matEmits = emits;
@@ -1306,10 +1334,69 @@ int rt_reset_materials(rt_context* ctx) {
     if (!ctx) return RT_ERR_ARG;
     if (!ctx->inited) { ctx->err = "rt_reset_materials before rt_init"; return RT_ERR_STATE; }
     if (int rc = sync_streams(ctx, false)) return rc;
+    // a texture-set binding keeps the table-reading kernels: their table goes back to the defaults
+    if (ctx->matTexBound)
+        if (int rc = write_mat_table(ctx, nullptr, ctx->matTex)) return rc;
     ctx->matCustom = false;  // the buffer stays allocated for the next set
     ctx->matEmits = false;
     ++ctx->matSerial;
     return RT_OK;
+}
+
+// ---------------------------------------------------------------- texture-set binding
+
+int rt_get_texture_sets(const rt_context* ctx, uint32_t* count) {
+    if (!ctx || !count) return RT_ERR_ARG;
+    *count = ctx->inited ? ctx->texSets : (ctx->textureSets > 0 ? (uint32_t)ctx->textureSets : 1u);
+    return RT_OK;
+}
+
+static int bind_material_textures(rt_context* ctx, const uint8_t (&next)[256]) {
+    // the kernels in flight read the table, and camera rays traced ahead precede it (spec_matches)
+    if (int rc = sync_streams(ctx, false)) return rc;
+    bool bound = false;
+    for (uint32_t id = 0; id < 256u; ++id) bound = bound || next[id] != 0u;
+    // without a binding and without a custom table no launch reads the device table
+    if (bound || ctx->matCustom)
+        if (int rc = write_mat_table(ctx, ctx->matCustom ? &ctx->matHost : nullptr, next)) return rc;
+    memcpy(ctx->matTex, next, 256);
+    ctx->matTexBound = bound;
+    ++ctx->matSerial;
+    return RT_OK;
+}
+
+int rt_set_material_textures(rt_context* ctx, uint32_t first_id, uint32_t count, const uint8_t* sets) {
+    if (!ctx || !sets) return RT_ERR_ARG;
+    if (count == 0u || (uint64_t)first_id + (uint64_t)count > 256u) {
+        ctx->err = "rt_set_material_textures: [first_id, first_id + count) must be a non-empty range of the ids 0..255";
+        return RT_ERR_ARG;
+    }
+    if (!ctx->inited) { ctx->err = "rt_set_material_textures before rt_init"; return RT_ERR_STATE; }
+    for (uint32_t k = 0; k < count; ++k)
+        if (sets[k] >= ctx->texSets) {
+            ctx->err = "rt_set_material_textures: entry " + std::to_string(first_id + k) + ": set " + std::to_string(sets[k]) +
+                       " of " + std::to_string(ctx->texSets) + " ([scene] textureSets)";
+            return RT_ERR_ARG;
+        }
+    uint8_t next[256];
+    memcpy(next, ctx->matTex, 256);
+    memcpy(next + first_id, sets, count);
+    return bind_material_textures(ctx, next);
+}
+
+int rt_get_material_textures(const rt_context* ctx, uint32_t first_id, uint32_t count, uint8_t* sets) {
+    if (!ctx || !sets) return RT_ERR_ARG;
+    if (count == 0u || (uint64_t)first_id + (uint64_t)count > 256u) return RT_ERR_ARG;
+    if (!ctx->inited) return RT_ERR_STATE;
+    memcpy(sets, ctx->matTex + first_id, count);
+    return RT_OK;
+}
+
+int rt_reset_material_textures(rt_context* ctx) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_reset_material_textures before rt_init"; return RT_ERR_STATE; }
+    const uint8_t none[256] = {};
+    return bind_material_textures(ctx, none);
 }
 
 // a context-stream user of the current LBVH waits for its build on the side stream
@@ -1544,6 +1631,12 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
     // mesh-level arrays the current mesh's (rt_set_mesh)
     const BvhBufs& set = ctx->bvh[ctx->bvhSet];
     const size_t NP = set.triCountPadded, B = set.B, P = (size_t)ctx->renderW * ctx->renderH;
+    if ((what & ~0xFF) != 0) {  // RT_ARR_TEX_SET(k): a colour map of texture set k
+        const int base = what & 0xFF;
+        const uint32_t k = (uint32_t)what >> 8;
+        const bool map = base == RT_ARR_TEX_ALBEDO_AO || base == RT_ARR_TEX_NORMAL_ROUGHNESS;
+        return what > 0 && map && k < ctx->texSets ? (size_t)kTexTexels * 8 : 0;
+    }
     switch (what) {
         case RT_ARR_VERTICES: return (size_t)ctx->nv * 12;
         case RT_ARR_INDICES: return (size_t)ctx->mesh.triCountPadded * 12;
@@ -1600,6 +1693,15 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
     if (!ctx || !dst) return RT_ERR_ARG;
     if (!ctx->inited) { ctx->err = "rt_download before rt_init"; return RT_ERR_STATE; }
     const void* src = nullptr;
+    if ((what & ~0xFF) != 0) {  // RT_ARR_TEX_SET(k) | RT_ARR_TEX_ALBEDO_AO / NORMAL_ROUGHNESS
+        const size_t need = rt_array_bytes(ctx, what);
+        if (need == 0) { ctx->err = "unknown array, or a texture set past [scene] textureSets"; return RT_ERR_ARG; }
+        if (bytes < need) { ctx->err = "destination too small"; return RT_ERR_ARG; }
+        if (int rc = sync_streams(ctx)) return rc;
+        const uint2* chain = (what & 0xFF) == RT_ARR_TEX_ALBEDO_AO ? ctx->fr.texAlbedo : ctx->fr.texNormal;
+        HIP_TRY(ctx, hipMemcpy(dst, chain + (size_t)((uint32_t)what >> 8) * kTexTexels, need, hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
     switch (what) {
         case RT_ARR_VERTICES: src = ctx->dVerts; break;
         case RT_ARR_INDICES: src = ctx->dIdx; break;

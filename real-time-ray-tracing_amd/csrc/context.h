@@ -361,6 +361,19 @@ struct rt_context {
     bool matEmits = false;              // an EMISSIVE entry of the custom table has a non-zero emission
     std::vector<rt_material> matHost;   // [256] the custom table's entries (empty until the first set)
     MatRecord* dMatTable = nullptr;     // [256], allocated by the first set
+    // texture sets: fr.texAlbedo / fr.texNormal hold texSets chains each, set k
+    // k * kTexTexels texels in.  matTex is the set each material id samples (rt_set_material_textures);
+    // all zeros (matTexBound false) is no binding and reaches no launch.  A bound set index travels in
+    // bits 16..23 of its id's MatRecord::typeFlags, so the device table is rewritten when either the
+    // material table or the binding changes, and a binding without a custom table runs the
+    // table-reading kernels over the defaults.
+    int textureSets = 0;                // [scene] textureSets as parsed (0: absent); checked by rt_init
+    uint32_t texSets = 1;               // the sets the context holds
+    uint8_t matTex[256] = {};
+    bool matTexBound = false;
+    // rt_upload_texture_set_device writes a set in place on the context stream: it waits there for what
+    // the other streams hold so far (texSide / texLean, recorded at the call) and they wait for texDone
+    hipEvent_t texSide = nullptr, texLean = nullptr, texDone = nullptr;
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
     // and the setters that change the stream drain it), and on a context without a post stream the

@@ -438,6 +438,9 @@ void update_dynamic_resolution(rt_context* ctx, float dt) {
     ctx->stripRows = h;
 }
 
+static int upload_texture_chain(rt_context* ctx, uint32_t set, int which, const uint16_t* texels, int width, int height,
+                                int channels);
+
 int rt_frame_init(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
     std::string err;
@@ -461,8 +464,9 @@ int rt_frame_init(rt_context* ctx) {
     ALLOC(fr.skyTree, (size_t)kSkyTreeNodes * 4);
     ALLOC(fr.sunTree, (size_t)kSunTreeNodes * 4);
     ALLOC(fr.lightSel, 16);
-    ALLOC(fr.texAlbedo, (size_t)kTexTexels * 8);
-    ALLOC(fr.texNormal, (size_t)kTexTexels * 8);
+    // texture sets ([scene] textureSets): the sets of one map are one allocation, set k k * kTexTexels in
+    ALLOC(fr.texAlbedo, (size_t)ctx->texSets * kTexTexels * 8);
+    ALLOC(fr.texNormal, (size_t)ctx->texSets * kTexTexels * 8);
     ALLOC(fr.texHeight, (size_t)kTexTexels * 2);
     HIP_TRY(ctx, hipMemset(fr.texHeight, 0, (size_t)kTexTexels * 2));
     const size_t P = (size_t)ctx->renderW * ctx->renderH;
@@ -590,6 +594,10 @@ int rt_frame_init(rt_context* ctx) {
         if ((rc2 = rt_upload_texture(ctx, RT_TEX_SOIL_ALBEDO_AO, t.albedoAo.data(), kTexSize, kTexSize, 4)) != RT_OK ||
             (rc2 = rt_upload_texture(ctx, RT_TEX_SOIL_NORMAL_ROUGHNESS, t.normalRough.data(), kTexSize, kTexSize, 4)) != RT_OK)
             return rc2;
+        // sets 1..N-1 start as copies of set 0's chains: a set nobody uploaded to renders like set 0
+        for (uint32_t k = 1; k < ctx->texSets; ++k)
+            for (uint2* map : {fr.texAlbedo, fr.texNormal})
+                HIP_TRY(ctx, hipMemcpy(map + (size_t)k * kTexTexels, map, (size_t)kTexTexels * 8, hipMemcpyDeviceToDevice));
     }
     HIP_TRY(ctx, hipMemset(fr.color, 0, P * 8));
     HIP_TRY(ctx, hipMemset(fr.normal, 0, P * 8));
@@ -621,11 +629,82 @@ int rt_upload_texture(rt_context* ctx, int which, const uint16_t* texels, int wi
     if (!ctx || !texels) return RT_ERR_ARG;
     FrameResources& fr = ctx->fr;
     if (!fr.texAlbedo) { ctx->err = "rt_upload_texture before rt_init"; return RT_ERR_STATE; }
+    return upload_texture_chain(ctx, 0u, which, texels, width, height, channels);
+}
+
+// rt_upload_texture for any texture set: the argument checks ahead of the state's
+int rt_upload_texture_set(rt_context* ctx, uint32_t set, int which, const uint16_t* texels, int width, int height,
+                          int channels) {
+    if (!ctx || !texels) return RT_ERR_ARG;
+    const bool map = which == RT_TEX_SOIL_ALBEDO_AO || which == RT_TEX_SOIL_NORMAL_ROUGHNESS;
+    if (!map && !(which == RT_TEX_SOIL_HEIGHT && set == 0u)) {
+        ctx->err = "rt_upload_texture_set: `which` must be the albedo/AO or the normal/roughness map (the height map is set 0's)";
+        return RT_ERR_ARG;
+    }
+    if (width != kTexSize || height != kTexSize || channels != (map ? 4 : 1)) {
+        ctx->err = "rt_upload_texture_set: the textures are 1024 x 1024, 4 channels (height: 1)";
+        return RT_ERR_ARG;
+    }
+    if (!ctx->inited) { ctx->err = "rt_upload_texture_set before rt_init"; return RT_ERR_STATE; }
+    if (set >= ctx->texSets) {
+        ctx->err = "rt_upload_texture_set: set " + std::to_string(set) + " of " + std::to_string(ctx->texSets) + " ([scene] textureSets)";
+        return RT_ERR_ARG;
+    }
+    return upload_texture_chain(ctx, set, which, texels, width, height, channels);
+}
+
+// The stream-ordered upload (texture.hip k_tex_ingest).  The set is written in place, so the write
+// follows every reader enqueued so far: the context stream's by stream order, the side stream's (the
+// shade kernel of pipelined frames and of synchronous draws' launches ahead) and the lean stream's by
+// events recorded here.  Later path traces read it on those streams: they wait for texDone.
+int rt_upload_texture_set_device(rt_context* ctx, const rt_texture_upload* u) {
+    if (!ctx || !u) return RT_ERR_ARG;
+    const char* bad = nullptr;
+    if (!u->texels) bad = "texels must not be NULL";
+    else if (u->which != RT_TEX_SOIL_ALBEDO_AO && u->which != RT_TEX_SOIL_NORMAL_ROUGHNESS)
+        bad = "`which` must be the albedo/AO or the normal/roughness map";
+    else if (u->format != RT_TEX_FORMAT_U16 && u->format != RT_TEX_FORMAT_U8) bad = "unknown format";
+    else if (((uintptr_t)u->texels & 3u) != 0u) bad = "texels must be 4-byte aligned";
+    if (bad) { ctx->err = std::string("rt_upload_texture_set_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_upload_texture_set_device before rt_init"; return RT_ERR_STATE; }
+    if (u->set >= ctx->texSets) {
+        ctx->err = "rt_upload_texture_set_device: set " + std::to_string(u->set) + " of " + std::to_string(ctx->texSets) +
+                   " ([scene] textureSets)";
+        return RT_ERR_ARG;
+    }
+    for (hipEvent_t* e : {&ctx->texSide, &ctx->texLean, &ctx->texDone})
+        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    hipStream_t s = ctx->stream;
+    if (u->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)u->ready_event, 0));
+    if (ctx->sideStream) {
+        HIP_TRY(ctx, hipEventRecord(ctx->texSide, ctx->sideStream));
+        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->texSide, 0));
+    }
+    if (ctx->leanStream) {
+        HIP_TRY(ctx, hipEventRecord(ctx->texLean, ctx->leanStream));
+        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->texLean, 0));
+    }
+    uint2* chain = (u->which == RT_TEX_SOIL_ALBEDO_AO ? ctx->fr.texAlbedo : ctx->fr.texNormal) + (size_t)u->set * kTexTexels;
+    HIP_TRY(ctx, rtk_launch_tex_ingest(u->texels, chain, (uint32_t)kTexSize * kTexSize, (int)u->format, s));
+    HIP_TRY(ctx, rtk_launch_mipgen((uint16_t*)chain, kTexSize, kTexLevels, 4, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->texDone, s));
+    if (ctx->sideStream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->texDone, 0));
+    if (ctx->leanStream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->leanStream, ctx->texDone, 0));
+    ++ctx->matSerial;  // what a synchronous draw traced ahead sampled the old texels (spec_matches)
+    return RT_OK;
+}
+
+}  // extern "C"
+
+// level 0 of one chain of texture set `set` from host memory, then its mips; synchronous
+static int upload_texture_chain(rt_context* ctx, uint32_t set, int which, const uint16_t* texels, int width, int height,
+                         int channels) {
+    FrameResources& fr = ctx->fr;
     uint16_t* chain = nullptr;
     int want = 4;
     switch (which) {
-        case RT_TEX_SOIL_ALBEDO_AO: chain = (uint16_t*)fr.texAlbedo; break;
-        case RT_TEX_SOIL_NORMAL_ROUGHNESS: chain = (uint16_t*)fr.texNormal; break;
+        case RT_TEX_SOIL_ALBEDO_AO: chain = (uint16_t*)(fr.texAlbedo + (size_t)set * kTexTexels); break;
+        case RT_TEX_SOIL_NORMAL_ROUGHNESS: chain = (uint16_t*)(fr.texNormal + (size_t)set * kTexTexels); break;
         case RT_TEX_SOIL_HEIGHT: chain = fr.texHeight; want = 1; break;
         default: ctx->err = "rt_upload_texture: unknown texture"; return RT_ERR_ARG;
     }
@@ -643,6 +722,8 @@ int rt_upload_texture(rt_context* ctx, int which, const uint16_t* texels, int wi
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
+
+extern "C" {
 
 namespace {
 // workspace slot k (1 .. kGbSets - 1): the camera outputs, and with `queues` the bounce queues with
@@ -762,9 +843,11 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
         // a custom material table (rt_set_materials): an id's class follows its entry, so every class;
         // the one table-reading variant is the all-classes kernels' on the unsplit plan (pt_bounce_plan
         // gives it for these two flags), and an emitter makes queue 4 a closest-hit queue
-        p.matTable = ctx->matCustom ? reinterpret_cast<const float4*>(ctx->dMatTable) : nullptr;
+        // ... and so does a texture-set binding (rt_set_material_textures), whose set index rides in the
+        // records: without a custom table they hold rt_default_material's entries
+        p.matTable = ctx->matCustom || ctx->matTexBound ? reinterpret_cast<const float4*>(ctx->dMatTable) : nullptr;
         if (p.matTable) p.ws.glossy = p.ws.microfacet = 1;
-        p.ws.closest4 = p.matTable && ctx->matEmits ? 1 : 0;
+        p.ws.closest4 = ctx->matCustom && ctx->matEmits ? 1 : 0;
     }
     return qs;
 }

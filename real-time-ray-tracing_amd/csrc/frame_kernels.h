@@ -316,6 +316,9 @@ extern "C" hipError_t rtk_hdr_out(const uint2* color, float4* hdr, size_t n, hip
 extern "C" hipError_t rtk_launch_sky(const SkyGenParams* p, hipStream_t stream);
 // MipmapGen (texture.hip): levels 1.. of a square 16-bit chain whose level 0 is in place
 extern "C" hipError_t rtk_launch_mipgen(uint16_t* chain, int size, int levels, int channels, hipStream_t stream);
+// level 0 of a 4-channel chain from device memory (rt_upload_texture_set_device): `texels` ushort4
+// (format 0, copied) or uchar4 (format 1, each channel v * 257) texels; texels a multiple of 2
+extern "C" hipError_t rtk_launch_tex_ingest(const void* src, uint2* dst, uint32_t texels, int format, hipStream_t stream);
 extern "C" hipError_t rtk_launch_scan(const float* in, float* out, float* sums, int size, int blockSize,
                                       hipStream_t stream);
 // Scan (scan.cuh:258-298) with the reference's postfix flag and size range (rt_scan_device)

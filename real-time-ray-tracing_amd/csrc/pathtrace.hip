@@ -170,17 +170,18 @@ RT_DEV void glossy(const PathCtx& c, RayState& rs, int k) {
     }
 }
 
-// one triplanar projection of DiffuseSurfaceInteraction's texture block
-RT_DEV void tri_plane(const PathTraceParams& P, F2 uv, float lod, F3 normal, F3 w, F3& alb, F3& nrm) {
+// one triplanar projection of DiffuseSurfaceInteraction's texture block; setOff: the first texel of the
+// hit's texture set in both maps (diffuse<.., kTab>; the constant 0 elsewhere)
+RT_DEV void tri_plane(const PathTraceParams& P, F2 uv, float lod, F3 normal, F3 w, F3& alb, F3& nrm, uint32_t setOff = 0u) {
     uv.x *= 0.5f;
     uv.y *= 0.5f;
-    const F4 t0 = sample_lod(P.texAlbedo, uv, lod);
+    const F4 t0 = sample_lod(P.texAlbedo, uv, lod, setOff);
     // scheduling fences: the gamma chain and the normal-map fetches would otherwise interleave,
     // and the live texels of both maps set the register peak of the shading kernels
     __builtin_amdgcn_sched_barrier(0);
     alb = f3(rt_powf_div(t0.x, 2.2f), rt_powf_div(t0.y, 2.2f), rt_powf_div(t0.z, 2.2f));  // rtmath.h log2_pair_t
     __builtin_amdgcn_sched_barrier(0);
-    const F4 t1 = sample_lod(P.texNormal, uv, lod);
+    const F4 t1 = sample_lod(P.texNormal, uv, lod, setOff);
     const F3 n = f3(t1.x - 0.5f, t1.y - 0.5f, t1.z - 0.5f);
     const F3 u = cross(normal, w);
     const F3 v = cross(normal, u);
@@ -204,7 +205,14 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     // RT_MAT_FLAG_FLAT: the texture block is skipped, the albedo is the entry's colour and the shading
     // normal stays the hit's interpolated one
     bool flat = false;
-    if constexpr (kTab) flat = ((__float_as_uint(mat_vec(P, rs.matId, 0).w) >> 8) & RT_MAT_FLAG_FLAT) != 0u;
+    // ... and bits 16..23 of the same word are the texture set bound to the id (rt_set_material_textures;
+    // the host writes only sets the context holds): one live register through the texture block
+    uint32_t setOff = 0u;
+    if constexpr (kTab) {
+        const uint32_t tf = __float_as_uint(mat_vec(P, rs.matId, 0).w);
+        flat = ((tf >> 8) & RT_MAT_FLAG_FLAT) != 0u;
+        setOff = ((tf >> 16) & 0xFFu) * kTexTexels;
+    }
     if (!flat) {
         const float lod = rt_log2f_div(rs.rayConeWidth * 0.5f * __builtin_sqrtf(1024.0f * 1024.0f + 1024.0f * 1024.0f));
         const float wx = surfaceNormal.x * surfaceNormal.x, wy = surfaceNormal.y * surfaceNormal.y,
@@ -218,7 +226,8 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
             else if (pl == 1) wv = fabsf(normal.x) > 0.999f ? f3(0, 0, 1) : f3(1, 0, 0);
             else wv = fabsf(normal.y) > 0.999f ? f3(1, 0, 0) : f3(0, 1, 0);
             F3 a, n;
-            tri_plane(P, uv, lod, normal, wv, a, n);
+            if constexpr (kTab) tri_plane(P, uv, lod, normal, wv, a, n, setOff);
+            else tri_plane(P, uv, lod, normal, wv, a, n);
             const float wgt = pl == 0 ? wx : pl == 1 ? wy : wz;
             accA = pl == 0 ? a * wgt : accA + a * wgt;
             accN = pl == 0 ? n * wgt : accN + n * wgt;

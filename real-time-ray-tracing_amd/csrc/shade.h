@@ -55,10 +55,12 @@ RT_DEV int wrap_repeat(int v, int size) {
     return (v < 0 && r == 0) ? size - 1 : r;
 }
 
-// SampleBicubicSmoothStep<Load2DFuncUshort4<Float4>, Float4, BoundaryFuncRepeat> on one mip level
-RT_DEV F4 bicubic_tex(const uint2* tex, int level, F2 uv) {
+// SampleBicubicSmoothStep<Load2DFuncUshort4<Float4>, Float4, BoundaryFuncRepeat> on one mip level.
+// setOff: the first texel of the chain's texture set (rt_upload_texture_set: set * kTexTexels), added
+// to the level's base in 32-bit arithmetic; the constant 0 everywhere but the table-reading kernels
+RT_DEV F4 bicubic_tex(const uint2* tex, int level, F2 uv, uint32_t setOff = 0u) {
     const int n = kTexSize >> level;
-    const uint32_t base = tex_level_offset(level);
+    const uint32_t base = tex_level_offset(level) + setOff;
     const F2 UV = {uv.x * (float)n, uv.y * (float)n};
     const float fx0 = floorf(UV.x - 0.5f), fy0 = floorf(UV.y - 0.5f);
     const F2 f = {UV.x - (fx0 + 0.5f), UV.y - (fy0 + 0.5f)};
@@ -89,13 +91,13 @@ RT_DEV F4 bicubic_tex(const uint2* tex, int level, F2 uv) {
     return o;
 }
 
-RT_DEV F4 sample_lod(const uint2* tex, F2 uv, float lod) {
+RT_DEV F4 sample_lod(const uint2* tex, F2 uv, float lod, uint32_t setOff = 0u) {
     const float low = floorf(lod);
     const float fr = lod - low;
     int lo = (int)low, hi = lo + 1;
     lo = lo < 0 ? 0 : lo > kTexLevels - 1 ? kTexLevels - 1 : lo;
     hi = hi < 0 ? 0 : hi > kTexLevels - 1 ? kTexLevels - 1 : hi;
-    const F4 a = bicubic_tex(tex, lo, uv), b = bicubic_tex(tex, hi, uv);
+    const F4 a = bicubic_tex(tex, lo, uv, setOff), b = bicubic_tex(tex, hi, uv, setOff);
     const float ia = 1.0f - fr;
     return F4{a.x * ia + b.x * fr, a.y * ia + b.y * fr, a.z * ia + b.z * fr, a.w * ia + b.w * fr};
 }

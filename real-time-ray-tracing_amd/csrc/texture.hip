@@ -32,7 +32,47 @@ __global__ __launch_bounds__(256) void k_mipgen(const uint16_t* __restrict__ in,
     }
 }
 
+// Level 0 of a ushort4 chain from device memory (rt_upload_texture_set_device): each lane writes two
+// texels, 16 bytes.  kU8: the source is uchar4 and each channel widens to v * 257 (255 -> 65535), else
+// it is ushort4 and copied.  The source is 4-byte aligned, a chain 8-byte (kTexTexels is odd): the
+// words are typed to those alignments and the compiler picks the widest access they allow.
+struct alignas(4) Words4 { uint32_t w[4]; };
+struct alignas(4) Words2 { uint32_t w[2]; };
+struct alignas(8) Texels2 { uint32_t w[4]; };
+
+__device__ inline uint32_t widen_pair(uint32_t lo, uint32_t hi) { return (lo * 257u) | ((hi * 257u) << 16); }
+
+template <bool kU8>
+__global__ __launch_bounds__(256) void k_tex_ingest(const void* __restrict__ src, uint2* __restrict__ dst, uint32_t pairs) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= pairs) return;
+    Texels2 o;
+    if constexpr (kU8) {
+        const Words2 q = reinterpret_cast<const Words2*>(src)[i];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t v = q.w[t];
+            o.w[2 * t] = widen_pair(v & 0xFFu, (v >> 8) & 0xFFu);
+            o.w[2 * t + 1] = widen_pair((v >> 16) & 0xFFu, v >> 24);
+        }
+    } else {
+        const Words4 q = reinterpret_cast<const Words4*>(src)[i];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o.w[t] = q.w[t];
+    }
+    reinterpret_cast<Texels2*>(dst)[i] = o;
+}
+
 }  // namespace
+
+extern "C" hipError_t rtk_launch_tex_ingest(const void* src, uint2* dst, uint32_t texels, int format, hipStream_t s) {
+    if (!src || !dst || texels == 0u || (texels & 1u) != 0u || (format != 0 && format != 1)) return hipErrorInvalidValue;
+    const uint32_t pairs = texels / 2u;
+    const dim3 grid((pairs + 255u) / 256u);
+    if (format == 1) hipLaunchKernelGGL(k_tex_ingest<true>, grid, dim3(256), 0, s, src, dst, pairs);
+    else hipLaunchKernelGGL(k_tex_ingest<false>, grid, dim3(256), 0, s, src, dst, pairs);
+    return hipGetLastError();
+}
 
 // levels 1..levels-1 of a square chain whose level 0 (size x size, C channels) is in place
 extern "C" hipError_t rtk_launch_mipgen(uint16_t* chain, int size, int levels, int channels, hipStream_t s) {

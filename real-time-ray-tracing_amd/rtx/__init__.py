@@ -114,6 +114,12 @@ class MaterialUpdate(C.Structure):
                 ("ready_event", C.c_void_p)]
 
 
+class TextureUpload(C.Structure):
+    """rt_texture_upload: one device texture upload (rt_upload_texture_set_device)."""
+    _fields_ = [("texels", C.c_void_p), ("set", C.c_uint32), ("which", C.c_int32), ("format", C.c_uint32),
+                ("ready_event", C.c_void_p)]
+
+
 class Material(C.Structure):
     """rt_material: one entry of the material table (rt_set_materials)."""
     _fields_ = [("type", C.c_int32), ("flags", C.c_uint32), ("color", C.c_float * 3), ("emission", C.c_float * 3),
@@ -131,6 +137,9 @@ class Material(C.Structure):
 
 MAT_LAMBERTIAN, MAT_MIRROR, MAT_GLASS, MAT_MICROFACET, MAT_EMISSIVE = range(5)  # RT_MAT_*
 MAT_FLAG_FLAT = 1  # RT_MAT_FLAG_FLAT
+TEXTURE_SETS_MAX = 16  # RT_TEXTURE_SETS_MAX
+TEX_FORMAT_U16, TEX_FORMAT_U8 = 0, 1  # RT_TEX_FORMAT_*
+TEX_SIZE = 1024  # the atlases are TEX_SIZE x TEX_SIZE, 4 channels
 
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
@@ -208,6 +217,12 @@ SIGNATURES = {
     "rt_set_materials": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material)]),
     "rt_get_materials": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material)]),
     "rt_reset_materials": (C.c_int, [C.c_void_p]),
+    "rt_get_texture_sets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rt_upload_texture_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "rt_upload_texture_set_device": (C.c_int, [C.c_void_p, C.POINTER(TextureUpload)]),
+    "rt_set_material_textures": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_get_material_textures": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_reset_material_textures": (C.c_int, [C.c_void_p]),
 }
 MAT_CLASS_GLOSSY, MAT_CLASS_MICROFACET = 1, 2  # RT_MAT_CLASS_*
 MAT_CLASS_ALL = MAT_CLASS_GLOSSY | MAT_CLASS_MICROFACET
@@ -252,7 +267,7 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
                  extra: str = "", max_size=(3840, 2160), camera_file: str | None = None, min_size=(640, 480),
                  target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None,
                  geometry_motion: bool | None = None, max_triangles: int | None = None,
-                 max_vertices: int | None = None) -> str:
+                 max_vertices: int | None = None, texture_sets: int | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
@@ -261,7 +276,9 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
     `geometry_motion`: [render] geometryMotion, the initial state of rt_set_geometry_motion (None:
     the key is not written, the default is off).
     `max_triangles` / `max_vertices`: [scene] maxTriangles / maxVertices, the capacity of set_mesh
-    (None: the keys are not written, the capacity is the init mesh)."""
+    (None: the keys are not written, the capacity is the init mesh).
+    `texture_sets`: [scene] textureSets, the texture sets the context holds (None: the key is not
+    written, one set)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -279,6 +296,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
             f.write("maxTriangles = %s\n" % max_triangles)
         if max_vertices is not None:
             f.write("maxVertices = %s\n" % max_vertices)
+        if texture_sets is not None:
+            f.write("textureSets = %s\n" % texture_sets)
         f.write("\n[render]\nspp = %d\n" % spp)
         if geometry_motion is not None:
             f.write("geometryMotion = %s\n" % ("true" if geometry_motion else "false"))
@@ -531,6 +550,63 @@ class RayTracer:
         """Back to the reference's constants: no custom table."""
         self._check(self.lib.rt_reset_materials(self.h), "rt_reset_materials")
 
+    # ---- texture sets (rt_upload_texture_set, rt_set_material_textures; include/rtx_amd.h)
+    @property
+    def texture_sets(self) -> int:
+        """The texture sets the context holds ([scene] textureSets; 1 without the key)."""
+        n = C.c_uint32()
+        self._check(self.lib.rt_get_texture_sets(self.h, C.byref(n)), "rt_get_texture_sets")
+        return n.value
+
+    def upload_texture_device(self, name: str, tensor_or_ptr, set: int, fmt: int, ready_event: int | None = None):
+        """Level 0 of map `name` of texture set `set` from device memory, stream-ordered (no host wait):
+        1024 x 1024 x 4 channels of uint16 (TEX_FORMAT_U16) or uint8 (TEX_FORMAT_U8, each channel
+        v * 257), given as a device pointer or an object with data_ptr() (a contiguous torch tensor,
+        whose size is checked).  ready_event as in update_vertices_device."""
+        if name not in ("SOIL_ALBEDO_AO", "SOIL_NORMAL_ROUGHNESS"):
+            raise ValueError("upload_texture_device: name must be SOIL_ALBEDO_AO or SOIL_NORMAL_ROUGHNESS")
+        if fmt not in (TEX_FORMAT_U16, TEX_FORMAT_U8):
+            raise ValueError("upload_texture_device: fmt must be TEX_FORMAT_U16 or TEX_FORMAT_U8")
+        if not 0 <= int(set) <= 0xFFFFFFFF:
+            raise ValueError("upload_texture_device: set must fit 32 bits")
+        ptr = tensor_or_ptr
+        if hasattr(tensor_or_ptr, "data_ptr"):
+            t = tensor_or_ptr
+            want = TEX_SIZE * TEX_SIZE * 4 * (2 if fmt == TEX_FORMAT_U16 else 1)
+            if t.numel() * t.element_size() != want or not t.is_contiguous():
+                raise ValueError("upload_texture_device: the tensor must be contiguous and hold %d bytes" % want)
+            ptr = t.data_ptr()
+        u = TextureUpload(int(ptr), int(set), TEX[name], int(fmt), ready_event)
+        self._check(self.lib.rt_upload_texture_set_device(self.h, C.byref(u)), "rt_upload_texture_set_device")
+
+    def set_material_textures(self, first_id: int, sets):
+        """Bind material ids [first_id, first_id + len(sets)) to texture sets (a sequence of set
+        indices); the other ids keep theirs.  Takes effect for every path trace enqueued after it."""
+        a = np.asarray(sets)
+        if a.size == 0:
+            a = np.zeros(0, np.uint8)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < 0 or a.max() > 255)):
+            raise ValueError("set_material_textures: sets must be a 1-D sequence of integers in 0..255")
+        if not 0 <= int(first_id) <= 0xFFFFFFFF:
+            raise ValueError("set_material_textures: first_id must fit 32 bits")
+        a = np.ascontiguousarray(a, np.uint8)
+        buf = a if a.size else np.zeros(1, np.uint8)
+        self._check(self.lib.rt_set_material_textures(self.h, int(first_id), int(a.size), buf.ctypes.data),
+                    "rt_set_material_textures")
+
+    def get_material_textures(self, first_id: int = 0, count: int = 256) -> np.ndarray:
+        """The texture set of ids [first_id, first_id + count) as a uint8 array."""
+        if not 0 <= int(first_id) <= 0xFFFFFFFF or not 0 <= int(count) <= 0xFFFFFFFF:
+            raise ValueError("get_material_textures: first_id and count must fit 32 bits")
+        out = np.zeros(max(int(count), 1) if int(count) <= 256 else 1, np.uint8)
+        self._check(self.lib.rt_get_material_textures(self.h, int(first_id), int(count), out.ctypes.data),
+                    "rt_get_material_textures")
+        return out[:int(count)]
+
+    def reset_material_textures(self):
+        """Every id back to set 0: no binding."""
+        self._check(self.lib.rt_reset_material_textures(self.h), "rt_reset_material_textures")
+
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")
 
@@ -648,16 +724,30 @@ class RayTracer:
     def save_image(self, path: str, kind: int = IMAGE_PPM_RGBA8):
         self._check(self.lib.rt_save_image(self.h, path.encode(), kind), "rt_save_image")
 
-    def upload_texture(self, name: str, texels: np.ndarray):
-        """init.cu:524-580: a 16-bit (H, W, C) level-0 image into the atlas; mips built on the device."""
+    def upload_texture(self, name: str, texels: np.ndarray, set: int = 0):
+        """init.cu:524-580: a 16-bit (H, W, C) level-0 image into the atlas; mips built on the device.
+        set: the texture set ([scene] textureSets) whose map is replaced; 0 is the soil atlas."""
         t = np.ascontiguousarray(texels, np.uint16)
+        if t.ndim not in (2, 3):
+            raise ValueError("upload_texture: texels must be (H, W) or (H, W, C)")
+        if not 0 <= int(set) <= 0xFFFFFFFF:
+            raise ValueError("upload_texture: set must fit 32 bits")
         h, w = t.shape[:2]
         c = 1 if t.ndim == 2 else t.shape[2]
-        self._check(self.lib.rt_upload_texture(self.h, TEX[name], t.ctypes.data, w, h, c), "rt_upload_texture")
+        if int(set) == 0:
+            self._check(self.lib.rt_upload_texture(self.h, TEX[name], t.ctypes.data, w, h, c), "rt_upload_texture")
+        else:
+            self._check(self.lib.rt_upload_texture_set(self.h, int(set), TEX[name], t.ctypes.data, w, h, c),
+                        "rt_upload_texture_set")
 
     # ---- downloads
-    def download(self, name: str, dtype=np.uint8) -> np.ndarray:
+    def download(self, name: str, dtype=np.uint8, set: int = 0) -> np.ndarray:
+        """Array `name`; set: the texture set of TEX_ALBEDO_AO / TEX_NORMAL_ROUGHNESS (RT_ARR_TEX_SET)."""
         what = ARR[name]
+        if set:
+            if name not in ("TEX_ALBEDO_AO", "TEX_NORMAL_ROUGHNESS") or not 0 < int(set) < (1 << 22):
+                raise ValueError("download: set applies to TEX_ALBEDO_AO / TEX_NORMAL_ROUGHNESS, as a small positive index")
+            what |= int(set) << 8
         n = self.lib.rt_array_bytes(self.h, what)
         buf = np.empty(n, dtype=np.uint8)
         self._check(self.lib.rt_download(self.h, what, buf.ctypes.data, n), "rt_download(%s)" % name)

@@ -30,7 +30,10 @@ through the host setter, and not at all (device_sets below); writes profiles/mat
 With --material-table: the cost of the table-reading kernel variant of rt_set_materials
 (material_table below); writes profiles/material_table.json.
 
-Usage: python tools/material_probe.py [--device-sets | --material-table] [--frames 100] [--repeats 5] [--out PATH]"""
+With --texture-sets: the cost of per-material texture sets (texture_sets below); writes
+profiles/texture_sets.json.
+
+Usage: python tools/material_probe.py [--device-sets | --material-table | --texture-sets] [--frames 100] [--repeats 5] [--out PATH]"""
 import argparse
 import json
 import os
@@ -233,6 +236,93 @@ def material_table(a):
     print(json.dumps(res))
 
 
+def texture_sets(a):
+    """--texture-sets: what sampling per-material texture sets costs (rt_set_material_textures, DESIGN.md
+    §4.1.5): pipelined 1080p 4-spp frames of the terrain under hashed(MIX8), in ONE context with four
+    texture sets, timed in turn --repeats times (medians of ms per frame).  Sets 1..3 are what rt_init
+    made them, device copies of the soil atlas in memory of their own: every series renders the same
+    pixels along the same paths (the queue lengths are compared), so the series differ by the addressing
+    and by the texture footprint alone.  (Other images change the shading normals and with them the
+    paths: a first version with random images traced 22 % fewer bounce rays and measured that instead.)
+
+      table         the defaults through rt_set_materials, no binding: the table-reading kernels at set 0
+      table_set1    the same with every id bound to set 1: one other atlas
+      table_4sets   id k bound to set k % 4: neighbouring hits sample different atlases
+      table_again   the first series again: the control
+
+    Writes profiles/texture_sets.json."""
+    import torch
+
+    import rtx
+    from rtx.frames import FramePipeline
+
+    w, h, spp, sets = 1920, 1080, 4, 4
+    dev = torch.device("cuda", 0)
+    prev = torch.cuda.current_stream(0)
+    names = ("table", "table_set1", "table_4sets", "table_again")
+    bind = dict(table=[0] * 256, table_set1=[1] * 256, table_4sets=[k % sets for k in range(256)], table_again=[0] * 256)
+    cfg = rtx.write_config(os.path.join(tempfile.mkdtemp(), "m.toml"), w, h, spp=spp, texture_sets=sets)
+    rt = rtx.RayTracer(w, h, cfg).init()
+    try:
+        rt.set_delta_time(16.667)
+        cam = rt.camera
+        cam.pos[:] = TERRAIN_CAM["pos"]
+        cam.yaw, cam.pitch = TERRAIN_CAM["yaw"], TERRAIN_CAM["pitch"]
+        rt.camera = cam
+        rt.set_triangle_materials(hashed(int(rt.info().triCount), MIX8))
+        rt.set_materials(0, [rtx.default_material(i) for i in range(256)])
+        fp = FramePipeline(rt, dev, pipelined=True)
+        state = dict(f=0)
+
+        def run(n):
+            for _ in range(n):
+                state["f"] += 1
+                fp.frame(state["f"])
+            fp.finish()
+
+        series = {name: [] for name in names}
+        for _ in range(a.repeats):
+            for name in names:
+                rt.set_material_textures(0, bind[name])  # a setter: it drains the pipeline first
+                run(a.warmup)
+                t0 = time.perf_counter()
+                run(a.frames)
+                series[name].append((time.perf_counter() - t0) * 1e3 / a.frames)
+        rows = {}
+        for name in names:
+            rt.set_material_textures(0, bind[name])
+            run((-state["f"]) % 256)  # every marked series at the same phase of the blue-noise sequence
+            run(a.warmup)
+            rt.frame_marks_begin(a.marked)
+            run(a.marked)
+            ms, n = rt.frame_marks_read()
+            q = rt.download("PT_QUEUE", np.uint32)
+            rows[name] = dict(ms_per_frame=float(np.median(series[name])), series_ms=series[name],
+                              sets_bound=sorted(set(bind[name])), last_chain=int(rt.info().lastChain),
+                              queue3_entries=int(q[0]), queue4_entries=int(q[1]), internal_errors=int(q[10]),
+                              marked_frames=n, kernel_ms={k: round(v, 4) for k, v in ms.items()})
+    finally:
+        rt.cleanup()
+        torch.cuda.set_stream(prev)
+    base = rows["table"]["ms_per_frame"]
+    res = dict(device=torch.cuda.get_device_name(0),
+               config="%dx%d, %d spp, terrain camera %r, pipelined FramePipeline, LBVH rebuild every frame, ids hashed(MIX8), "
+                      "%d texture sets, the material table the defaults" % (w, h, spp, TERRAIN_CAM, sets),
+               method="one context, the binding set between series; the four timed in turn %d times, %d frames each after "
+                      "%d warm-up frames; ms_per_frame is the median of the series; kernel_ms from %d frames bracketed by "
+                      "events" % (a.repeats, a.frames, a.warmup, a.marked),
+               series=rows,
+               same_queue_lengths=len({(r["queue3_entries"], r["queue4_entries"]) for r in rows.values()}) == 1,
+               set1_cost_ms=rows["table_set1"]["ms_per_frame"] - base,
+               four_sets_cost_ms=rows["table_4sets"]["ms_per_frame"] - base,
+               control_ms=rows["table_again"]["ms_per_frame"] - base)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "texture_sets.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "materials.json")
 
 
@@ -247,8 +337,12 @@ def main():
     ap.add_argument("--material-table", action="store_true",
                     help="time the table-reading kernel variant against the same ids without a custom table "
                          "(profiles/material_table.json)")
+    ap.add_argument("--texture-sets", action="store_true",
+                    help="time the table-reading kernels under texture-set bindings (profiles/texture_sets.json)")
     ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
+    if a.texture_sets:
+        return texture_sets(a)
     if a.device_sets:
         return device_sets(a)
     if a.material_table:
