@@ -44,7 +44,9 @@ typedef struct rt_context rt_context;
  * the reference's [resolution] / [file] / [optimziation] tables; extensions: [scene]
  * chunkDim (VoxelsGenerator::kChunkDim, terrain.h:42), [render] spp, [render] device, [render]
  * geometryMotion (true | false, default false: rt_set_geometry_motion's initial state; any other
- * value is refused with RT_ERR_IO).
+ * value is refused with RT_ERR_IO), [render] emitterSampling (true | false, default false) and [render]
+ * emitterProbability (a number in [0, 1], default 0.5): rt_set_emitter_sampling's initial state; an
+ * unparsable or out-of-range value is refused with RT_ERR_IO.
  * [tuning] (scheduling A/B aids; the defaults are the measured best): arena (bool),
  * streams ("cumask" | "prio"), tracePerCu / trace4PerCu (0: automatic), trace3ShortPerCu (a short queue
  * 3's workgroups per CU on one GPU; 0: all of them), chain ("serial" | "off" |
@@ -476,6 +478,45 @@ int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32
 int rt_set_geometry_motion(rt_context* ctx, int on);
 int rt_get_geometry_motion(const rt_context* ctx, int* on);
 
+/* Emitter sampling: next-event estimation of the emissive triangles of a custom material table
+ * (DESIGN.md §4.1.6).  Off by default, and then nothing changes.  The path tracer takes one light sample
+ * per diffuse interaction; with emitter sampling on, that sample goes with probability `probability`
+ * (q) to an emitting triangle and otherwise to the sun or sky as before, whose pdf is scaled by 1 - q.
+ * q is the emitters' counterpart of the reference's sky-against-sun choice; it counts as 0 while the
+ * list is empty.
+ *
+ * The emitter list is built on the device behind every LBVH build while the feature is on and a custom
+ * material table (rt_set_materials) holds an EMISSIVE entry with non-zero emission; otherwise a frame
+ * launches exactly the kernels it launches without the feature.  Triangle t of the build is an emitter
+ * when the id the path tracer reads for it ([render] materialOverride, else its rt_set_triangle_materials*
+ * entry, else 3) has type EMISSIVE and its weight, area x (0.2126 r + 0.7152 g + 0.0722 b) of the entry's
+ * emission, is > 0.  An emitter is selected in proportion to its weight and a point on it uniformly by
+ * area; emitters are two-sided, as a camera ray sees them.  A shadow ray towards an emitter lights its
+ * sample only when its closest hit is exactly that triangle.
+ *
+ * The list belongs to the build: it follows rt_update_vertices* and rt_set_mesh* (areas) and the
+ * triangle ids set on the device, and frames in flight keep the list of the build they trace.  A change
+ * of the material table or of the triangle ids shows in the list at the next build, which draws do every
+ * frame; until then a listed triangle that stopped emitting reads as occluded, and a new emitter is
+ * reached by bounce rays only.
+ *
+ * rt_set_emitter_sampling waits for the streams like the other setters (what a synchronous draw traced
+ * ahead is dropped), allocates the list buffers on the first enable, by the triangle capacity, and takes
+ * effect from the next LBVH build.  Meshes of more than 2^20 triangles get no list.
+ * Errors, in this order, with nothing changed: RT_ERR_ARG: NULL argument; RT_ERR_ARG: probability not
+ * finite or outside [0, 1]; RT_ERR_STATE: rt_set_emitter_sampling before rt_init; RT_ERR_HIP: the
+ * allocation failed. */
+int rt_set_emitter_sampling(rt_context* ctx, int on, float probability);
+int rt_get_emitter_sampling(const rt_context* ctx, int* on, float* probability);
+/* The device kernels' own statement of the two rules, compiled for the host (no context).
+ * rt_emitter_weight: the weight of the triangle xyz = v0 | v1 | v2 under `emission`, in fp32:
+ * 0.5 |(v1 - v0) x (v2 - v0)| x luminance.  rt_emitter_select: the slot that r in [0, 1) selects from
+ * the inclusive CDF of `count` >= 1 weights, the first whose CDF value is >= r * cdf[count - 1], and the
+ * probability the CDF gives it, (cdf[slot] - cdf[slot - 1]) / cdf[count - 1].  RT_ERR_ARG: NULL
+ * argument, or count 0. */
+int rt_emitter_weight(const float xyz[9], const float emission[3], float* weight);
+int rt_emitter_select(const float* cdf, uint32_t count, float r, uint32_t* slot, float* prob);
+
 /* Per-triangle materials: SceneMaterial::materialsIdx (kernel.cuh:198-203, init.cu:261-269), the
  * material id the path tracer looks up at every hit (traverse.cuh:29-32).  ids[k] is the material of
  * triangle first + k, the objectIdx a hit reports; [first, first + count) lies within triCount
@@ -565,9 +606,9 @@ uint32_t rt_material_class_rule(uint32_t id);
  *   microfacet: f0 and alpha are the entry's; glass: etaT = ior; mirror: no parameter;
  *   emissive: a path that ends on the hit (a camera or bounce ray, not an occluded shadow ray) carries
  *     `emission` where a sky hit carries the environment, ahead of the path tracer's clamp at 10.
- *     Emitters are NOT sampled as lights: next-event estimation of emissive triangles is out of scope,
- *     shadow rays towards the sun or sky that hit an emitter stay occluded, and an emitter lights the
- *     scene only through the bounce rays that land on it.
+ *     By default emitters are not sampled as lights: shadow rays towards the sun or sky that hit an
+ *     emitter stay occluded, and an emitter lights the scene only through the bounce rays that land on
+ *     it.  rt_set_emitter_sampling (below) adds next-event estimation of the emissive triangles.
  * The mask of RT_BUF_RENDER_COLOR stays the id, and [render] materialOverride still chooses the id,
  * whose entry then supplies the parameters (its low 8 bits index the table).
  *
@@ -803,7 +844,11 @@ enum rt_array_name {
                                     [23] entries of the step-3 queue's shading list (bounce rays that
                                     hit a triangle; 0 when resume<3> runs unsplit or as the fused chain) */
     RT_ARR_PT_Q3_ORIGINS = 33,   /* float4[cap] step-3 queue rays of the last launch: origin xyz, pixel bits */
-    RT_ARR_PT_Q3_DIRS = 34,      /* float4[cap] direction xyz, flags bits ([0] of RT_ARR_PT_QUEUE are valid) */
+    RT_ARR_PT_Q3_DIRS = 34,      /* float4[cap] direction xyz, flags bits ([0] of RT_ARR_PT_QUEUE are valid).
+                                    Flags: bit 0 the entry is a shadow ray, bits 1..6 its sample index; bit 7
+                                    (emitter sampling only) the shadow ray samples an emitter, and then bits
+                                    8..31 are that light's triangle index; without bit 7, bits 16..31 are the
+                                    light id: 7777 none (a bounce ray), 9999 the environment */
     RT_ARR_PT_Q4_ORIGINS = 35,   /* float4[cap] step-4 queue, same layout ([1] valid) */
     RT_ARR_PT_Q4_DIRS = 36,
     RT_ARR_PT_STATS = 31,        /* uint32[W*H][4] rays, node visits, triangle tests, diffuse events
@@ -820,9 +865,17 @@ enum rt_array_name {
     RT_ARR_ADJ_OFFSETS = 43,     /* uint32[nv + 1] first slot of each vertex in the vertex -> corner adjacency
                                     (rt_mesh_adjacency) */
     RT_ARR_CORNER_SLOTS = 44,    /* uint32[3 * triCountPadded] each corner's slot in it */
-    RT_ARR_TRI_MATERIAL_CENSUS = 45 /* uint32[256] triangles per material id of the current table over [0, triCount):
+    RT_ARR_TRI_MATERIAL_CENSUS = 45, /* uint32[256] triangles per material id of the current table over [0, triCount):
                                     the device census after rt_set_triangle_materials_device, the host's after
                                     rt_set_triangle_materials, triCount at id 3 without a table */
+    /* the emitter list of the last LBVH build (rt_set_emitter_sampling); all three have size 0 while
+       emitter sampling is off or that build wrote no list */
+    RT_ARR_EMITTER_TRIS = 46,    /* uint32[count] the emitting triangles, ascending */
+    RT_ARR_EMITTER_WEIGHTS = 47, /* float[count] their weights (rt_emitter_weight) */
+    RT_ARR_EMITTER_CDF = 48,     /* float[P] the reference Scan (inclusive, block 256) of the weights zero-padded
+                                    to P, the power of two >= max(triCount, 256); P from rt_array_bytes */
+    RT_ARR_PT_Q3_BETA = 49       /* float4[cap] step-3 queue: the first diffuse interaction's throughput beta1 xyz,
+                                    ray-cone spread ([0] of RT_ARR_PT_QUEUE are valid) */
 };
 /* RT_ARR_TEX_ALBEDO_AO and RT_ARR_TEX_NORMAL_ROUGHNESS OR-ed with RT_ARR_TEX_SET(k) name the chain of
  * texture set k (k = 0 is the plain name); a k past the context's sets is RT_ERR_ARG (rt_array_bytes: 0). */

@@ -16,6 +16,7 @@
 #include <fstream>
 #include <sstream>
 
+#include "emitter_kernels.h"
 #include "gaussian_tables.h"
 #include "mat_kernels.h"
 #include "rtmath.h"
@@ -386,6 +387,24 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
         }
         ctx->geomMotion = v->raw == "true";
     }
+    if (const rttoml::Value* v = rttoml::find(doc, "render", "emitterSampling")) {
+        if (v->isArray || v->isString || (v->raw != "true" && v->raw != "false")) {
+            g_createError = "config parse error: [render] emitterSampling must be true or false";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->emitterOn = v->raw == "true";
+    }
+    if (const rttoml::Value* v = rttoml::find(doc, "render", "emitterProbability")) {
+        char* end = nullptr;
+        const float q = v->isArray || v->isString || v->raw.empty() ? -1.0f : strtof(v->raw.c_str(), &end);
+        if (!end || *end != '\0' || !std::isfinite(q) || q < 0.0f || q > 1.0f) {
+            g_createError = "config parse error: [render] emitterProbability must be a number in [0, 1]";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->emitterQ = q;
+    }
     ctx->bvhSkipPublish = (uint32_t)rttoml::find_or_int(doc, "debug", "bvhSkipPublish", -1);
     ctx->bvhSkipBuilds = rttoml::find_or_int(doc, "debug", "bvhSkipPublishBuilds", -1);
     ctx->bvhWaitMs = rttoml::find_or_float(doc, "debug", "bvhWaitMs", 1000.0f);
@@ -587,6 +606,7 @@ int rt_init(rt_context* ctx) {
     for (hipEvent_t* e : {&ctx->queryDone[0], &ctx->queryDone[1]})
         HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (ctx->geomMotion && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;  // [render] geometryMotion
+    if (ctx->emitterOn && (rc = ensure_emitter_lists(ctx)) != RT_OK) return rc;    // [render] emitterSampling
     // mesh sets (rt_set_mesh*, mesh.hip): the staging buffers of the host variants and the adjacency
     // sort's scratch, behind every other buffer of rt_init, so that a set only enqueues work
     if ((rc = dalloc(ctx, &ctx->dVertStage, capNV * 12)) != RT_OK) return rc;
@@ -805,6 +825,41 @@ int rt_build_bvh(rt_context* ctx) {
         }
         ctx->built = true;
         ctx->builtEpoch = ctx->geomEpoch;
+    }
+    // emitter sampling: the set's emitter list from the records this build has just written, behind it on
+    // its stream and ahead of buildDone, so whatever traces the set reads the list of its build.  The
+    // material table is written in place behind a wait for every stream; the triangle ids may come from a
+    // device set on another stream (matDone), and a later device set into the buffer read here waits for
+    // listRead as it waits for the path traces that read it.
+    {
+        BvhBufs& b = ctx->bvh[ctx->bvhSet];
+        b.emBuilt = false;
+        if (emitter_active(ctx) && b.emHeader && ctx->mesh.triCount <= kEmMaxTris) {
+            const bool ids = ctx->materialOverride < 0 && ctx->dTriMat;
+            if (ids && ctx->matDevice && ctx->matDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->matDone, 0));
+            EmitterListParams e;
+            e.triPos = b.triPos;
+            e.triMat = ids ? ctx->dTriMat : nullptr;
+            e.matTable = reinterpret_cast<const float4*>(ctx->dMatTable);
+            e.materialOverride = ctx->materialOverride;
+            e.triCount = ctx->mesh.triCount;
+            e.cdfLen = emitter_cdf_len(ctx->mesh.triCount);
+            e.triWeight = b.emTriWeight;
+            e.blockCount = b.emBlockCount;
+            e.tris = b.emTris;
+            e.weights = b.emWeights;
+            e.cdf = b.emCdf;
+            e.scanSums = b.emScanSums;
+            e.header = b.emHeader;
+            HIP_TRY(ctx, rtk_launch_emitter_list(&e, stream));
+            if (ids && ctx->matPoolReady) {
+                rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+                HIP_TRY(ctx, hipEventRecord(tab.listRead, stream));
+                tab.listValid = true;
+            }
+            b.emBuilt = true;
+            b.emCdfLen = e.cdfLen;
+        }
     }
     if (ctx->postStream) {
         HIP_TRY(ctx, hipEventRecord(ctx->buildDone[ctx->bvhSet], stream));
@@ -1029,6 +1084,69 @@ int rt_get_geometry_motion(const rt_context* ctx, int* on) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- emitter sampling
+//
+// The list buffers of the LBVH sets that exist (the second set's are allocated with it,
+// ensure_bvh_pair), by the triangle capacity: every triangle may be an emitter.  Once allocated they stay.
+int ensure_emitter_lists(rt_context* ctx) {
+    if (ctx->capTri > kEmMaxTris) return RT_OK;  // such a mesh gets no list (rt_build_bvh); nothing to hold
+    const size_t len = emitter_cdf_len(ctx->capTri), blocks = len / 256;
+    for (BvhBufs& b : ctx->bvh)
+        if (b.nodes && !b.emHeader) {
+            int rc;
+            if ((rc = dalloc(ctx, &b.emTris, len * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emWeights, len * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emCdf, len * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emTriWeight, len * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emBlockCount, (blocks + 1) * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emScanSums, blocks * 4)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.emHeader, kEmHeaderWords * 4)) != RT_OK) return rc;  // last: the set is complete
+        }
+    return RT_OK;
+}
+
+int rt_set_emitter_sampling(rt_context* ctx, int on, float probability) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!std::isfinite(probability) || probability < 0.0f || probability > 1.0f) {
+        ctx->err = "rt_set_emitter_sampling: probability must be finite and lie in [0, 1]";
+        return RT_ERR_ARG;
+    }
+    if (!ctx->inited) { ctx->err = "rt_set_emitter_sampling before rt_init"; return RT_ERR_STATE; }
+    // the kernels in flight read the lists, and what a synchronous draw traced ahead precedes the change
+    int rc = sync_streams(ctx, false);
+    if (rc != RT_OK) return rc;
+    if (on && (rc = ensure_emitter_lists(ctx)) != RT_OK) return rc;
+    // from the next build on: a synchronous draw's prebuild was made under the old state
+    ctx->bvhPrebuilt = false;
+    if (!on)
+        for (BvhBufs& b : ctx->bvh) b.emBuilt = false;
+    ctx->emitterOn = on != 0;
+    ctx->emitterQ = probability;
+    return RT_OK;
+}
+
+int rt_get_emitter_sampling(const rt_context* ctx, int* on, float* probability) {
+    if (!ctx || !on || !probability) return RT_ERR_ARG;
+    *on = ctx->emitterOn ? 1 : 0;
+    *probability = ctx->emitterQ;
+    return RT_OK;
+}
+
+// the kernels' two rules (emitter_kernels.h), compiled for the host
+int rt_emitter_weight(const float xyz[9], const float emission[3], float* weight) {
+    if (!xyz || !emission || !weight) return RT_ERR_ARG;
+    *weight = emitter_weight(xyz, emission);
+    return RT_OK;
+}
+
+int rt_emitter_select(const float* cdf, uint32_t count, float r, uint32_t* slot, float* prob) {
+    if (!cdf || !slot || !prob || count == 0u) return RT_ERR_ARG;
+    float p;
+    *slot = emitter_select(cdf, count, r, p);
+    *prob = p;
+    return RT_OK;
+}
+
 // ---------------------------------------------------------------- per-triangle materials
 //
 // SceneMaterial::materialsIdx (kernel.cuh:198-203, init.cu:261-269): one material id per triangle,
@@ -1131,7 +1249,7 @@ static int ensure_mat_pool(rt_context* ctx) {
     for (hipEvent_t* e : {&ctx->matSrc, &ctx->matDone})
         if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (rt_context::MatTable& t : ctx->matPool)
-        for (hipEvent_t* e : {&t.read, &t.specRead})
+        for (hipEvent_t* e : {&t.read, &t.specRead, &t.listRead})
             if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     uint8_t* at = block;
     for (rt_context::MatTable& t : ctx->matPool)
@@ -1185,6 +1303,7 @@ int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* 
     // stream (an earlier device set) or behind a wait for every stream (a host set)
     if (dst.readValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.read, 0));
     if (dst.specValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.specRead, 0));
+    if (dst.listValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.listRead, 0));  // an emitter-list build (rt_build_bvh)
     MatSetParams p;
     p.prev = ctx->dTriMat;  // null after rt_set_mesh* and a reset: 3 everywhere
     p.src = u->ids;
@@ -1205,7 +1324,7 @@ int rt_set_triangle_materials_device(rt_context* ctx, const rt_material_update* 
     // the caller's later work on the context stream follows the read of its buffer, and so does every
     // later path trace: its kernels run on this stream, on the context stream or behind a fork of it
     if (s != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->matDone, 0));
-    dst.readValid = dst.specValid = false;
+    dst.readValid = dst.specValid = dst.listValid = false;
     ctx->matCur = next;
     ctx->dTriMat = dst.ids;
     ctx->triMatClasses = classes;  // the plan of later frames: exactly the declared bits
@@ -1681,7 +1800,21 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
         case RT_ARR_PT_Q3_ORIGINS:
         case RT_ARR_PT_Q3_DIRS:
         case RT_ARR_PT_Q4_ORIGINS:
-        case RT_ARR_PT_Q4_DIRS: return (size_t)ctx->fr.ws.cap * 16;
+        case RT_ARR_PT_Q4_DIRS:
+        case RT_ARR_PT_Q3_BETA: return (size_t)ctx->fr.ws.cap * 16;
+        // the emitter list of the current set's last build; nothing while that build wrote none.  The
+        // count is known on the device only: read behind a wait for the streams
+        case RT_ARR_EMITTER_TRIS:
+        case RT_ARR_EMITTER_WEIGHTS: {
+            if (!set.emBuilt) return 0;
+            rt_context* mctx = const_cast<rt_context*>(ctx);
+            uint32_t count = 0;
+            if (sync_streams(mctx, false) != RT_OK ||
+                hipMemcpy(&count, set.emHeader + kEmCount, 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return 0;
+            return (size_t)count * 4;
+        }
+        case RT_ARR_EMITTER_CDF: return set.emBuilt ? (size_t)set.emCdfLen * 4 : 0;
         case RT_ARR_TRI_MATERIALS: return (size_t)ctx->mesh.triCount;
         case RT_ARR_TRI_MATERIAL_CENSUS: return 256 * sizeof(uint32_t);
         default: return 0;
@@ -1748,6 +1881,10 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_PT_Q3_DIRS: src = ctx->fr.camQ3[ctx->fr.lastSlot].rayD; break;
         case RT_ARR_PT_Q4_ORIGINS: src = ctx->fr.camQ4[ctx->fr.lastSlot].rayO; break;
         case RT_ARR_PT_Q4_DIRS: src = ctx->fr.camQ4[ctx->fr.lastSlot].rayD; break;
+        case RT_ARR_PT_Q3_BETA: src = ctx->fr.camQ3[ctx->fr.lastSlot].st1; break;
+        case RT_ARR_EMITTER_TRIS: src = ctx->bvh[ctx->bvhSet].emTris; break;
+        case RT_ARR_EMITTER_WEIGHTS: src = ctx->bvh[ctx->bvhSet].emWeights; break;
+        case RT_ARR_EMITTER_CDF: src = ctx->bvh[ctx->bvhSet].emCdf; break;
         case RT_ARR_SUN_DIR: {
             if (bytes < 16) { ctx->err = "destination too small"; return RT_ERR_ARG; }
             float* o = (float*)dst;
@@ -1786,6 +1923,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, ctx->bvh[ctx->bvhSet].triCountPadded, hipMemcpyDeviceToHost));
         return RT_OK;
     }
+    if (need == 0) return RT_OK;  // an empty emitter list, or none
     HIP_TRY(ctx, hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
     if (what == RT_ARR_NODES || what == RT_ARR_TLAS_NODES) {
         // the reference's q3 (idxLeft, idxRight, isLeftLeaf, isRightLeaf) from the child references

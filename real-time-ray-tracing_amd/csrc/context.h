@@ -45,6 +45,18 @@ struct BvhBufs {
     // context's counts being the current mesh's.  tlasNodes and triPos follow B (rt_build_bvh).
     uint32_t triCount = 0, triCountPadded = 0, B = 0;
     uint64_t meshSerial = 0;    // rt_context::meshSerial at that build
+    // emitter sampling (rt_set_emitter_sampling): the set's emitter list, written behind
+    // its build on the build's stream (emitter_kernels.h), so every reader of the set reads the list of
+    // the build it traces.  Allocated on the first enable, by the triangle capacity.
+    uint32_t* emTris = nullptr;
+    float* emWeights = nullptr;
+    float* emCdf = nullptr;
+    uint32_t* emHeader = nullptr;
+    float* emTriWeight = nullptr;    // scratch of the list build
+    uint32_t* emBlockCount = nullptr;
+    float* emScanSums = nullptr;
+    bool emBuilt = false;       // the set's last build wrote a list; the path traces on it sample emitters
+    uint32_t emCdfLen = 0;      // ... whose CDF has this length (emitter_cdf_len of that build's triCount)
 };
 
 // G-buffer sets in flight with frame pipelining: with four, frame f+4's camera rays wait for the
@@ -343,7 +355,8 @@ struct rt_context {
         uint32_t* census = nullptr;     // [256] triangles per id over [0, triCount), of the last device set into it
         hipEvent_t read = nullptr;      // behind the last path trace that read it, on the context stream
         hipEvent_t specRead = nullptr;  // behind the last shade kernel a synchronous draw launched ahead on it (side stream)
-        bool readValid = false, specValid = false;
+        hipEvent_t listRead = nullptr;  // behind the last emitter-list build that read it (the build's stream)
+        bool readValid = false, specValid = false, listValid = false;
     } matPool[kMatPool];
     int matCur = 0;
     size_t matBytes = 0;                // capNP rounded up to 16
@@ -361,6 +374,12 @@ struct rt_context {
     bool matEmits = false;              // an EMISSIVE entry of the custom table has a non-zero emission
     std::vector<rt_material> matHost;   // [256] the custom table's entries (empty until the first set)
     MatRecord* dMatTable = nullptr;     // [256], allocated by the first set
+    // emitter sampling (rt_set_emitter_sampling): while on and the custom table emits
+    // (emitter_active), every LBVH build is followed by its emitter list (BvhBufs::em*), and a path trace
+    // on a set that has one runs the kNee kernels with the chance emitterQ
+    bool emitterOn = false;             // [render] emitterSampling
+    float emitterQ = 0.5f;              // [render] emitterProbability
+    uint64_t prebuiltMatSerial = 0;     // matSerial at a synchronous draw's prebuild: its list is that table's
     // texture sets: fr.texAlbedo / fr.texNormal hold texSets chains each, set k
     // k * kTexTexels texels in.  matTex is the set each material id samples (rt_set_material_textures);
     // all zeros (matTexBound false) is no binding and reaches no launch.  A bound set index travels in
@@ -467,6 +486,8 @@ extern "C" size_t rt_alloc_bytes(const rt_context* ctx, int name);  // frame.cpp
 extern "C" void bvh_select(rt_context* ctx, int k);  // context.cpp: point the dTriPos.. views at bvh[k]
 extern "C" void arena_place(rt_context* ctx, BvhBufs& b);  // context.cpp: set b takes the current mesh's counts and arena layout
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
+extern "C" int ensure_emitter_lists(rt_context* ctx);  // context.cpp: the existing LBVH sets' emitter-list buffers
+inline bool emitter_active(const rt_context* ctx) { return ctx->emitterOn && ctx->matCustom && ctx->matEmits; }
 extern "C" int ensure_geometry_motion(rt_context* ctx);  // context.cpp: dPrevVerts and the existing LBVH sets' triDisp
 std::string rt_data_dir();
 void rt_camera_update(const rt_camera& in, int renderW, int renderH, HostCamera& c);

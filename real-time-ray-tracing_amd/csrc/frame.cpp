@@ -848,6 +848,14 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
         p.matTable = ctx->matCustom || ctx->matTexBound ? reinterpret_cast<const float4*>(ctx->dMatTable) : nullptr;
         if (p.matTable) p.ws.glossy = p.ws.microfacet = 1;
         p.ws.closest4 = ctx->matCustom && ctx->matEmits ? 1 : 0;
+        // emitter sampling: the list of the build this launch traces, when that build wrote one
+        const BvhBufs& set = ctx->bvh[ctx->bvhSet];
+        if (emitter_active(ctx) && set.emBuilt && p.matTable) {
+            p.emHeader = set.emHeader;
+            p.emTris = set.emTris;
+            p.emCdf = set.emCdf;
+            p.emitterQ = ctx->emitterQ;
+        }
     }
     return qs;
 }
@@ -1281,6 +1289,7 @@ int prebuild_next_bvh(rt_context* ctx) {
     bvh_select(ctx, cur);
     ctx->bvhPrebuilt = rc == RT_OK;
     ctx->prebuiltEpoch = ctx->geomEpoch;
+    ctx->prebuiltMatSerial = ctx->matSerial;
     return rc;
 }
 
@@ -1375,7 +1384,9 @@ int enqueue_frame(rt_context* ctx, uint32_t* target, uint32_t pitch, bool hdr) {
     rt_input_control_update(ctx, dt);  // UpdateFrame's InputControlUpdate (kernel.cu:117)
     ctx->fr.drawDt = dt;
     // built beside the previous synchronous frame, from the geometry this frame draws
-    if (ctx->bvhPrebuilt && !ctx->postStream && ctx->prebuiltEpoch == ctx->geomEpoch) {
+    // (with emitter sampling the build carries a list of the triangle materials too: also from this table)
+    if (ctx->bvhPrebuilt && !ctx->postStream && ctx->prebuiltEpoch == ctx->geomEpoch &&
+        (!emitter_active(ctx) || ctx->prebuiltMatSerial == ctx->matSerial)) {
         ctx->bvhPrebuilt = false;
         bvh_select(ctx, ctx->bvhSet ^ 1);  // the path trace waits for its build (wait_bvh)
     } else if ((rc = rt_build_bvh(ctx)) != RT_OK) {
@@ -1504,6 +1515,7 @@ int ensure_bvh_pair(rt_context* ctx) {
         }
     }
 #undef ALLOC
+    if (ctx->emitterOn && (rc = ensure_emitter_lists(ctx)) != RT_OK) return rc;  // else with rt_set_emitter_sampling
     // lowest priority: it should fill what the trace chain leaves idle
     if (!ctx->sideStream && (rc = rt_create_stream(ctx, &ctx->sideStream, false)) != RT_OK) return rc;
     for (hipEvent_t* e : {&ctx->buildDone[0], &ctx->buildDone[1], &ctx->bvhFree[0], &ctx->bvhFree[1]})

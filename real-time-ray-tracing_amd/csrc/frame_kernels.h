@@ -66,6 +66,12 @@ struct HistCamera { float pos[3], left[3], up[3], dir[3]; };  // HistoryCamera (
 // has matType MAT_SKY), so the queue tracer ends those traversals at their first hit.  (The one
 // exception: emitters of a custom material table, PtWorkspace::closest4.)
 constexpr uint32_t kQShadowFlag = 1u;
+// rayD.w bits 1..6: the sample index.  Bit 7 (emitter sampling, launches with PathTraceParams::emHeader):
+// the shadow ray samples an emitter, and bits 8..31 are that light's triangle index; such a ray runs to
+// its closest hit in both queues, since only a closest hit on exactly that triangle lights the sample.
+// Without bit 7, bits 16..31 are the light id (7777: none, 9999: the environment).
+constexpr uint32_t kQEmitterFlag = 1u << 7;
+constexpr int kQEmitterShift = 8;
 
 // Whether the resume of a queue-3 entry can reach the diffuse interaction D1: only a bounce ray
 // (not a shadow ray) that hit a triangle gets a diffuse material (update_material); every other
@@ -215,6 +221,15 @@ struct PathTraceParams {
     // one of a context without the feature; set: the table-reading kernels (kTab of k_pt_shade0 and
     // k_pt_resume), always with ws.glossy and ws.microfacet
     const float4* matTable;
+    // emitter sampling (rt_set_emitter_sampling): the emitter list of the LBVH build the
+    // launch traces (emitter_kernels.h: header = count, bits of the CDF's total; the emitters' triangle
+    // indices; the inclusive CDF of their weights) and the chance q that a light sample goes to it.
+    // emHeader null: the launch sequence of a context without the feature; set (only with matTable): the
+    // kNee variants of the table-reading kernels and of the two queue tracers
+    const uint32_t* emHeader;
+    const uint32_t* emTris;
+    const float* emCdf;
+    float emitterQ;
 };
 
 // One entry of the device material table, 64 B: each of its vectors is one aligned 16-byte load of the

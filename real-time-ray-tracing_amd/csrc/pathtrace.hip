@@ -21,6 +21,7 @@
 // With spp > 1 sample s uses frame index spp*(frameNum-1)+1+s and the demodulated colour and
 // albedo are averaged in fp32, in sample order, before the half store;
 // the other G-buffers come from sample 0.
+#include "emitter_kernels.h"
 #include "frame_kernels.h"
 #include "pt_common.h"
 #include "queue_fetch.h"
@@ -35,6 +36,10 @@ namespace {
 constexpr uint32_t kQShadow = kQShadowFlag;  // isShadowRay
 constexpr int kQSampleShift = 1;           // sample index s (6 bits, spp <= 64)
 constexpr int kQLightShift = 16;           // lightIdx (16 bits: 7777 or 9999)
+// emitter sampling (kNee): RayState::lightIdx of a shadow ray that samples an emitter is the light's
+// triangle index with this bit on top, which neither light id (7777, 9999) nor a hit's objectIdx has; in
+// a queue entry it travels as kQEmitterFlag with the index in bits 8..31 (frame_kernels.h)
+constexpr int kEmLightBit = 0x40000000;
 
 struct RayState {
     F3 orig, dir, pos, normal, fakeNormal, albedo, centerRaydir;
@@ -87,7 +92,10 @@ RT_DEV float4 mat_vec(const PathTraceParams& P, int id, int k) { return P.matTab
 // kTab: the launch carries a custom material table (rt_set_materials; P.matTable set).  The type,
 // colour, GGX parameters, index of refraction and emission of a hit then come from its entry instead
 // of the reference's constants; instantiated on the all-classes kernels only.
-template <bool kTab = false>
+// kNee: the launch samples emitters (P.emHeader set).  A shadow ray then reaches its light only when it
+// names that light: an emitter ray the EMISSIVE triangle it sampled and nothing else, an environment ray
+// the sky; an environment ray that meets an emitter stays occluded, as without the feature.
+template <bool kTab = false, bool kNee = false>
 RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
     // values first, one store each: stores sunk behind a branch became a private array
     // materialsIdx[objectIdx] (traverse.cuh:29-32): P.triMat, or 3 everywhere without a table
@@ -102,7 +110,10 @@ RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
     rs.matId = rs.hit ? id : 99999;
     rs.matType = rs.hit ? type : MAT_SKY;
     if (rs.isShadowRay) {
-        if ((rs.matType == EMISSIVE && rs.lightIdx == rs.objectIdx) || (rs.matType == MAT_SKY && rs.lightIdx == kEnvLightId))
+        // (hit: a miss has objectIdx -1, whose bits would pass for any emitter index)
+        const bool lit = kNee ? (rs.hit && rs.matType == EMISSIVE && rs.lightIdx == (rs.objectIdx | kEmLightBit))
+                              : (rs.matType == EMISSIVE && rs.lightIdx == rs.objectIdx);
+        if (lit || (rs.matType == MAT_SKY && rs.lightIdx == kEnvLightId))
             rs.hitLight = true;
         else
             rs.isOccluded = true;
@@ -116,7 +127,7 @@ RT_DEV void update_material(const PathTraceParams& P, RayState& rs) {
 RT_DEV bool needs_trace(const RayState& rs) { return !(rs.hitLight || !rs.isHitProcessed || rs.isOccluded); }
 
 // ... and what it does with the hit
-template <bool kTab = false>
+template <bool kTab = false, bool kNee = false>
 RT_DEV void apply_hit(const PathTraceParams& P, RayState& rs, const HitInfo& h) {
     rs.isHitProcessed = false;
     rs.offset = h.offset;
@@ -129,7 +140,7 @@ RT_DEV void apply_hit(const PathTraceParams& P, RayState& rs, const HitInfo& h) 
     rs.hit = h.hit;
     rs.depth = h.t;
     if (rs.hit) rs.rayConeWidth += rs.rayConeSpread * h.t;
-    update_material<kTab>(P, rs);
+    update_material<kTab, kNee>(P, rs);
 }
 
 // GlossySurfaceInteraction (surfaceInteraction.cuh:11-34, bsdf.cuh:130-165); random number rn[0][k]
@@ -192,7 +203,36 @@ RT_DEV void tri_plane(const PathTraceParams& P, F2 uv, float lod, F3 normal, F3 
 // rn[2*bounce+1].  kMF: the material table can hold the microfacet material (id 4: materialOverride
 // or a triangle's entry, rt_material_classes); without it the GGX branch, whose live values set the
 // kernels' register peak, is not compiled in.
-template <bool kMF, bool kTab = false>
+// One light sample on the emitter list: the slot by emitter_select's rule from rSel,
+// a point on that triangle's record by the square-root warp of (r0, r1), and the solid-angle pdf of the
+// one-sample rule, q P_k dist^2 / (area |n . dir|); emitters are two-sided.  A degenerate triangle or a
+// grazing direction gives an infinite or NaN pdf, which diffuse()'s guards end like any other.
+RT_DEV void sample_emitter(const PathTraceParams& P, F3 from, uint32_t count, float q, float r0, float r1, float rSel,
+                           F3& dir, float& pdf, int& lightIdx) {
+    float prob;
+    const uint32_t slot = emitter_select(P.emCdf, count, rSel, prob);
+    const uint32_t tri = P.emTris[slot];
+    const float4* tp = P.triPos + 4u * tri;
+    const float4 a = tp[0], b = tp[1], d = tp[2];
+    const float xyz[9] = {a.x, a.y, a.z, b.x, b.y, b.z, d.x, d.y, d.z};
+    float cr[3];
+    emitter_cross(xyz, cr);
+    const float area = emitter_area(cr);
+    const float su = __builtin_sqrtf(r0);
+    const float u = 1.0f - su, v = r1 * su;
+    const F3 v0 = f3(a.x, a.y, a.z);
+    const F3 p = v0 + (f3(b.x, b.y, b.z) - v0) * u + (f3(d.x, d.y, d.z) - v0) * v;
+    const F3 to = p - from;
+    const float dist2 = to.x * to.x + to.y * to.y + to.z * to.z;
+    dir = to / __builtin_sqrtf(dist2);
+    const float cosL = fabsf(cr[0] * dir.x + cr[1] * dir.y + cr[2] * dir.z) / (2.0f * area);  // |n . dir|, n = cr / |cr|
+    pdf = q * prob * dist2 / (area * cosL);
+    lightIdx = (int)tri | kEmLightBit;
+}
+
+// kNee: the launch samples emitters (P.emHeader set): the random numbers r2[2] and r2[3], unused
+// otherwise, choose between the emitter list and the environment and select the emitter.
+template <bool kMF, bool kTab = false, bool kNee = false>
 RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     if (rs.hitLight || !rs.isDiffuse || rs.isOccluded) return;
     const PathTraceParams& P = c.P;
@@ -251,7 +291,18 @@ RT_DEV void diffuse(PathCtx& c, int bounce, RayState& rs, F3& beta) {
     F3 lDir;
     float lPdf = 1.0f;
     int lIdx;
-    sample_light(P, c.sunDir, lDir, lPdf, lIdx, r2[0], r2[1], c.skyTree, c.sunTree);
+    if constexpr (kNee) {
+        const uint32_t emCount = P.emHeader[kEmCount];
+        const float q = emCount != 0u ? P.emitterQ : 0.0f;  // an empty list is never sampled
+        if (r2[2] < q) {
+            sample_emitter(P, rs.pos, emCount, q, r2[0], r2[1], r2[3], lDir, lPdf, lIdx);
+        } else {
+            sample_light(P, c.sunDir, lDir, lPdf, lIdx, r2[0], r2[1], c.skyTree, c.sunTree);
+            lPdf = lPdf * (1.0f - q);  // at q = 0 the product with 1: the same bits
+        }
+    } else {
+        sample_light(P, c.sunDir, lDir, lPdf, lIdx, r2[0], r2[1], c.skyTree, c.sunTree);
+    }
     F3 sDir, sBsdf, lBsdf, tmp;
     float sPdf = 0.0f;
     if (!kMF || rs.matType == LAMBERTIAN) {
@@ -340,10 +391,10 @@ RT_DEV void gbuffer_step0(const PathCtx& c, PathVars& v) {
 // tracer), applied before the loop so that the record is dead by the first interaction.  An
 // intersection at a step >= kDeferFrom is not traced here: the step is returned and the caller
 // queues the ray.  Returns 5 when the path is complete.
-template <int kDeferFrom, bool kMF, bool kTab = false>
+template <int kDeferFrom, bool kMF, bool kTab = false, bool kNee = false>
 RT_DEV int run_path(PathCtx& c, PathVars& v, int k0, const HitInfo* hit, const SceneView& sc, uint2* stk) {
     RayState& rs = v.rs;
-    if (hit) apply_hit<kTab>(c.P, rs, *hit);
+    if (hit) apply_hit<kTab, kNee>(c.P, rs, *hit);
 #pragma unroll 1
     for (int k = k0; k < 5; ++k) {
         if ((k != k0 || !hit) && needs_trace(rs)) {
@@ -353,7 +404,7 @@ RT_DEV int run_path(PathCtx& c, PathVars& v, int k0, const HitInfo* hit, const S
             intersect(sc, rs.orig, rs.dir, stk, 256, h);
             c.visits += h.visits;
             c.tests += h.tests;
-            apply_hit<kTab>(c.P, rs, h);
+            apply_hit<kTab, kNee>(c.P, rs, h);
         }
         if (k == 0) gbuffer_step0(c, v);
         if (k == 4) break;
@@ -361,7 +412,7 @@ RT_DEV int run_path(PathCtx& c, PathVars& v, int k0, const HitInfo* hit, const S
         if (k >= 2) {
             const bool first = k == 2;
             F3 beta = f3(1.0f);
-            diffuse<kMF, kTab>(c, first ? 0 : 1, rs, beta);
+            diffuse<kMF, kTab, kNee>(c, first ? 0 : 1, rs, beta);
             if (first) {
                 v.beta1 = beta;
                 v.outNormal = rs.fakeNormal;
@@ -393,8 +444,8 @@ RT_DEV int run_shade0_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
 }
 
 // end of PathTrace (pathtrace.cuh:103-128): the sample's demodulated colour
-// kTab: a path that ends on an emissive hit carries its entry's emission (emitters are not sampled
-// as lights: only a camera or bounce ray that lands on one sees it)
+// kTab: a path that ends on an emissive hit carries its entry's emission: a camera or bounce ray that
+// lands on one, or with emitter sampling (kNee kernels) a shadow ray that reached the emitter it sampled
 template <bool kTab = false>
 RT_DEV F3 finish(const PathCtx& c, const PathVars& v) {
     const RayState& rs = v.rs;
@@ -443,10 +494,15 @@ RT_DEV uint32_t wave_append(bool want, uint32_t* counter) {
     return base + lane_rank(m);
 }
 
+template <bool kNee = false>
 RT_DEV void enqueue(const PtQueue& q, uint32_t slot, const PathVars& v, uint32_t pixel, uint32_t s) {
     const RayState& rs = v.rs;
-    const uint32_t flags = (rs.isShadowRay ? kQShadow : 0u) | (s << kQSampleShift) |
-                           ((uint32_t)rs.lightIdx << kQLightShift);
+    uint32_t flags = (rs.isShadowRay ? kQShadow : 0u) | (s << kQSampleShift) |
+                     ((uint32_t)rs.lightIdx << kQLightShift);
+    if constexpr (kNee) {  // a shadow ray to an emitter: kQEmitterFlag and the light's triangle index
+        if ((rs.lightIdx & kEmLightBit) != 0)
+            flags = kQShadow | (s << kQSampleShift) | kQEmitterFlag | ((uint32_t)(rs.lightIdx & ~kEmLightBit) << kQEmitterShift);
+    }
     q.rayO[slot] = make_float4(rs.orig.x, rs.orig.y, rs.orig.z, __uint_as_float(pixel));
     q.rayD[slot] = make_float4(rs.dir.x, rs.dir.y, rs.dir.z, __uint_as_float(flags));
     q.st0[slot] = make_float4(rs.albedo.x, rs.albedo.y, rs.albedo.z, rs.rayConeWidth);
@@ -738,7 +794,8 @@ RT_DEV uint32_t claim_next(ShadeClaim& c, uint32_t* counters, uint32_t& slot) {
 //
 // kTab: the launch carries a custom material table (rt_set_materials): the all-classes kernel reading
 // the table.  A trailing, defaulted parameter: the other instantiations compile exactly as before.
-template <bool kGlossy, bool kMF, bool kOneRound, bool kTab = false>
+// kNee: ... and the launch samples emitters (P.emHeader; rt_set_emitter_sampling), likewise.
+template <bool kGlossy, bool kMF, bool kOneRound, bool kTab = false, bool kNee = false>
 #ifndef RTX_SHADE_WAVES  // A/B builds only (tools/abl_build.sh): waves per SIMD of the default-material variant
 #define RTX_SHADE_WAVES 3
 #endif
@@ -802,7 +859,8 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
                 finalize_hit(sc, v.rs.orig, v.rs.dir, hr.x, (int)__float_as_uint(hr.y), hr.z, hr.w, P.ws.hit0Err[q],
                              h);
                 static_assert(!kTab || kGlossy, "the table variant is the all-classes kernel's");
-                if constexpr (kGlossy) kd = run_path<3, kMF, kTab>(c, v, 0, &h, sc, stk + tid);
+                static_assert(!kNee || kTab, "emitters are entries of a custom table");
+                if constexpr (kGlossy) kd = run_path<3, kMF, kTab, kNee>(c, v, 0, &h, sc, stk + tid);
                 else kd = run_shade0_diffuse<kMF>(c, v, h);
                 if (kd < 3) {  // cannot happen without mirror/glass materials: flag it, finish the sample
                     atomicAdd(&P.ws.counters[kCntError], 1u);
@@ -822,7 +880,7 @@ __global__ __launch_bounds__(256, (kGlossy || !kOneRound) ? 2 : RTX_SHADE_WAVES)
                 }
                 if (kd < 5) {
                     ++c.rays;  // the deferred RaySceneIntersect
-                    enqueue(kd == 3 ? P.ws.q3 : P.ws.q4, kd == 3 ? slot3 : slot4, v, p, (uint32_t)s);
+                    enqueue<kNee>(kd == 3 ? P.ws.q3 : P.ws.q4, kd == 3 ? slot3 : slot4, v, p, (uint32_t)s);
                     outL.w = 1.0f;
                 } else {
                     const F3 Ls = finish<kTab>(c, v);
@@ -951,12 +1009,12 @@ __global__ __launch_bounds__(256) void k_pt_geom_motion(PathTraceParams P) {
 // run_path<0, kMF>(c, v, kStep, &hit, ..) in straight line where no glossy interaction can run:
 // step 4 (it ends the path) for any table, step 3 without mirror or glass (as run_shade0_diffuse:
 // G3 returns at once, so step 3 is D1 and step 4 traces exactly when D1 produced a ray)
-template <int kStep, bool kMF, bool kTab = false>
+template <int kStep, bool kMF, bool kTab = false, bool kNee = false>
 RT_DEV int resume_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
-    apply_hit<kTab>(c.P, v.rs, hit);
+    apply_hit<kTab, kNee>(c.P, v.rs, hit);
     if (kStep == 4) return 5;
     F3 beta = f3(1.0f);
-    diffuse<kMF, kTab>(c, 1, v.rs, beta);
+    diffuse<kMF, kTab, kNee>(c, 1, v.rs, beta);
     v.beta0 = beta;
     return needs_trace(v.rs) ? 4 : 5;
 }
@@ -964,6 +1022,7 @@ RT_DEV int resume_diffuse(PathCtx& c, PathVars& v, const HitInfo& hit) {
 // Entry i of a bounce queue: reloads the sample's state and turns the hit the tracer found (t,
 // triangle index bits, u, v; errorT) into the HitInfo of its intersection.  Shared by resume_entry
 // and the lean pass of the split resume<3>.
+template <bool kNee = false>
 RT_DEV void reload_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
                          PathVars& v, uint32_t& p, uint32_t& s, HitInfo& h) {
     const PathTraceParams& P = c.P;
@@ -979,6 +1038,9 @@ RT_DEV void reload_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint
     rs.dir = f3(d.x, d.y, d.z);
     rs.isShadowRay = (flags & kQShadow) != 0u;
     rs.lightIdx = (int)(flags >> kQLightShift);
+    if constexpr (kNee) {
+        if ((flags & kQEmitterFlag) != 0u) rs.lightIdx = (int)(flags >> kQEmitterShift) | kEmLightBit;
+    }
     rs.albedo = f3(s0.x, s0.y, s0.z);
     rs.rayConeWidth = s0.w;
     v.beta1 = f3(s1.x, s1.y, s1.z);
@@ -997,13 +1059,13 @@ RT_DEV void reload_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint
 // Entry i of queue kStep (3 or 4): reloads the sample's state, applies the hit the tracer found
 // and runs the rest of its sequence.  Returns 4 when the I4 ray must be traced (kStep == 3 only),
 // else 5 (the sample is complete).  kGlossy: the material table holds mirror or glass.
-template <int kStep, bool kMF, bool kGlossy, bool kTab = false>
+template <int kStep, bool kMF, bool kGlossy, bool kTab = false, bool kNee = false>
 RT_DEV int resume_entry(PathCtx& c, const PtQueue& q, const SceneView& sc, uint32_t i, float4 hr, float herr,
                         PathVars& v, uint32_t& p, uint32_t& s) {
     HitInfo h;
-    reload_entry(c, q, sc, i, hr, herr, v, p, s, h);
-    if constexpr (kGlossy && kStep == 3) return run_path<0, kMF, kTab>(c, v, kStep, &h, sc, nullptr);
-    else return resume_diffuse<kStep, kMF, kTab>(c, v, h);
+    reload_entry<kNee>(c, q, sc, i, hr, herr, v, p, s, h);
+    if constexpr (kGlossy && kStep == 3) return run_path<0, kMF, kTab, kNee>(c, v, kStep, &h, sc, nullptr);
+    else return resume_diffuse<kStep, kMF, kTab, kNee>(c, v, h);
 }
 
 // a completed sample of a queue entry: its radiance goes to the late-resolve slot
@@ -1020,7 +1082,7 @@ RT_DEV void store_path_L(const PathCtx& c, const PathVars& v, uint32_t p, uint32
 // Called by every lane of the wave (wave_append); an idle lane passes active = false, kd = 5.
 // Adds the lane's counts to the caller's rays and rsD (the latter in detail launches only) and
 // returns its queue-4 slot.
-template <bool kTab = false>
+template <bool kTab = false, bool kNee = false>
 RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd, uint32_t p, uint32_t s, uint32_t& rays,
                              uint32_t& rsD) {
     const PathTraceParams& P = c.P;
@@ -1028,7 +1090,7 @@ RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd,
     if (active) {
         if (kd < 5) {  // out of step 3 only
             ++c.rays;
-            enqueue(P.ws.q4, slot, v, p, s);
+            enqueue<kNee>(P.ws.q4, slot, v, p, s);
         } else {
             store_path_L<kTab>(c, v, p, s);
         }
@@ -1046,7 +1108,7 @@ RT_DEV uint32_t finish_entry(PathCtx& c, const PathVars& v, bool active, int kd,
 // One workgroup of a resume kernel: the samples of queue kStep (3 or 4) once k_trace_queue has
 // written their hits.  kListed (queue 3, no mirror or glass): not the queue in order but its
 // entries on the shading list ws.shade3, one listed entry per lane.
-template <int kStep, bool kMF, bool kGlossy, bool kListed, bool kTab = false>
+template <int kStep, bool kMF, bool kGlossy, bool kListed, bool kTab = false, bool kNee = false>
 RT_DEV void resume_queue(const PathTraceParams& P) {
     static_assert(!kListed || (kStep == 3 && !kGlossy), "the shading list is queue 3's, kept without glossy tables");
     __shared__ uint32_t sob[256];
@@ -1078,9 +1140,9 @@ RT_DEV void resume_queue(const PathTraceParams& P) {
         uint32_t p = 0, s = 0;
         if (active) {
             const uint32_t i = kListed ? P.ws.shade3[li] : li;
-            kd = resume_entry<kStep, kMF, kGlossy, kTab>(c, q, sc, i, hitRec[i], hitErr[i], v, p, s);
+            kd = resume_entry<kStep, kMF, kGlossy, kTab, kNee>(c, q, sc, i, hitRec[i], hitErr[i], v, p, s);
         }
-        finish_entry<kTab>(c, v, active, kd, p, s, rays, rsD);
+        finish_entry<kTab, kNee>(c, v, active, kd, p, s, rays, rsD);
     }
     if (kStep == 3 && P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays);
@@ -1089,10 +1151,13 @@ RT_DEV void resume_queue(const PathTraceParams& P) {
 // Queue kStep taken in order: queue 4 always, queue 3 when it keeps no shading list.
 // kTab: under a custom material table (rt_set_materials), the all-classes body reading the table.  Step 4
 // shades nothing; its variant differs in finish() only (the emission of the entry the path ended on).
-template <int kStep, bool kMF, bool kGlossy, bool kTab = false>
+// kNee: ... and the launch samples emitters (P.emHeader): step 3 takes its light sample from the list too,
+// and both steps tell an emitter shadow ray's hit on its own light from any other (update_material).
+template <int kStep, bool kMF, bool kGlossy, bool kTab = false, bool kNee = false>
 __global__ __launch_bounds__(256, kStep == 3 ? (kGlossy ? 2 : 3) : 4) void k_pt_resume(PathTraceParams P) {
     static_assert(!kTab || kStep == 4 || (kMF && kGlossy), "the table variant is the all-classes kernel's");
-    resume_queue<kStep, kMF, kGlossy, false, kTab>(P);
+    static_assert(!kNee || kTab, "emitters are entries of a custom table");
+    resume_queue<kStep, kMF, kGlossy, false, kTab, kNee>(P);
 }
 
 // The split resume<3> (ws.shade3 set; default materials or the microfacet one): of the queue-3
@@ -1406,9 +1471,12 @@ dim3 shade_grid(const PathTraceParams* p, K kernel, int& cached) {
 
 template <bool kOneRound>
 void launch_shade_rounds(const PathTraceParams* p, hipStream_t stream) {
-    static int occ[5];
+    static int occ[6];
     const dim3 pb(256);
-    if (p->matTable) {  // a custom material table (rt_set_materials): every class, parameters from the table
+    if (p->emHeader) {  // emitter sampling: the table-reading kernel that also samples the emitter list
+        auto k = k_pt_shade0<true, true, kOneRound, true, true>;
+        hipLaunchKernelGGL(k, shade_grid(p, k, occ[5]), pb, 0, stream, *p);
+    } else if (p->matTable) {  // a custom material table (rt_set_materials): every class, parameters from the table
         auto k = k_pt_shade0<true, true, kOneRound, true>;
         hipLaunchKernelGGL(k, shade_grid(p, k, occ[4]), pb, 0, stream, *p);
     } else if (p->ws.glossy && p->ws.microfacet) {  // a triangle table with both classes (rt_set_triangle_materials)
@@ -1497,6 +1565,8 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
     const PtBouncePlan plan = pt_bounce_plan(p->ws);
     // a custom table has the unsplit kernels only: the host sets both classes with it (fill_pt_params)
     if (p->matTable && plan != PtBouncePlan::unsplit) return hipErrorInvalidValue;
+    // emitter sampling rides on the table-reading kernels, with a list to sample
+    if (p->emHeader && (!p->matTable || !p->emTris || !p->emCdf)) return hipErrorInvalidValue;
     if (plan == PtBouncePlan::chain) {
         // kernel 2 = the fused bounce chain (trace<3> .. resume<4>); slots 3-5 stay empty, so the
         // hook's kernel numbers and the per-kernel timing slots keep their meaning
@@ -1521,6 +1591,7 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
                 (void)kernel(p->ws.microfacet ? k_pt_resume3_shade<true> : k_pt_resume3_shade<false>, pg, stream);
                 return forked ? hipSuccess : kernel(k_pt_resume3_lean, pg, stream);
             }
+            if (p->emHeader) return kernel(k_pt_resume<3, true, true, true, true>, pg, stream);
             if (p->matTable) return kernel(k_pt_resume<3, true, true, true>, pg, stream);
             return kernel(p->ws.glossy       ? (p->ws.microfacet ? k_pt_resume<3, true, true> : k_pt_resume<3, false, true>)
                           : p->ws.microfacet ? k_pt_resume<3, true, false>
@@ -1529,7 +1600,11 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
         if (e == hipSuccess) e = stage([&] { return rtk_launch_trace_queue(p, 4, stream); });
         // step 4 shades nothing; under a custom table it reads the emission of the entry a path ended on
         if (e == hipSuccess)
-            e = stage([&] { return kernel(p->matTable ? k_pt_resume<4, false, false, true> : k_pt_resume<4, false, false>, pg, stream); });
+            e = stage([&] {
+                return kernel(p->emHeader   ? k_pt_resume<4, false, false, true, true>
+                              : p->matTable ? k_pt_resume<4, false, false, true>
+                                            : k_pt_resume<4, false, false>, pg, stream);
+            });
         if (e == hipSuccess && forked) e = hipStreamWaitEvent(stream, fork->done, 0);  // its pathL stores
         if (e != hipSuccess) return e;
     }

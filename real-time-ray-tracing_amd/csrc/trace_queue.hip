@@ -47,7 +47,10 @@ RT_DEV void flush_shade_list(const PathTraceParams& P, uint32_t* shl, uint32_t n
 // kStats: the launch keeps per-pixel statistics (P.statsOut), so the traversal counts visits and tests
 // kClosest (queue 4 under a custom material table with an emitter, PtWorkspace::closest4): a bounce
 // ray's traversal runs to its closest hit, since which triangle it lands on decides the sample's colour
-template <int kStep, bool kStats, bool kClosest = false>
+// kNee (emitter sampling, PathTraceParams::emHeader): a shadow ray that samples an emitter (kQEmitterFlag)
+// runs to its closest hit too, in both queues: the first hit of a BVH-ordered traversal may be the light
+// behind an occluder, or an occluder behind the light
+template <int kStep, bool kStats, bool kClosest = false, bool kNee = false>
 __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) {
     __shared__ uint2 stk[17 * kTraceBlock];  // 16 entries + the dead slot trav_step stores above the top
     __shared__ uint32_t shadeList[kStep == 3 ? kTraceBlock : 1];  // per wave: 64 pending shading-list entries
@@ -105,6 +108,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
                     rec = trav_first_rec(sc);
                     active = true;
                     occlusion = (kStep == 4 && !kClosest) || (__float_as_uint(d.w) & kQShadowFlag) != 0u;
+                    if constexpr (kNee) occlusion = occlusion && (__float_as_uint(d.w) & kQEmitterFlag) == 0u;
                 } else if (none) {
                     exhausted = true;
                 }
@@ -190,6 +194,11 @@ extern "C" hipError_t rtk_launch_trace_queue(const PathTraceParams* p, int step,
     void (*k)(PathTraceParams) = step == 3 ? (stats ? k_trace_queue<3, true> : k_trace_queue<3, false>)
                                            : (stats ? k_trace_queue<4, true> : k_trace_queue<4, false>);
     if (step == 4 && p->ws.closest4) k = stats ? k_trace_queue<4, true, true> : k_trace_queue<4, false, true>;
+    if (p->emHeader) {  // emitter sampling: with a custom table that emits, so queue 4 is a closest-hit queue already
+        if (!p->ws.closest4) return hipErrorInvalidValue;
+        k = step == 3 ? (stats ? k_trace_queue<3, true, false, true> : k_trace_queue<3, false, false, true>)
+                      : (stats ? k_trace_queue<4, true, true, true> : k_trace_queue<4, false, true, true>);
+    }
     hipLaunchKernelGGL(k, grid, dim3(kTraceBlock), 0, stream, *p);
     return hipGetLastError();
 }

@@ -27,7 +27,8 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            SUN_PDF=22, SUN_CDF=23, SUN_DIR=24, HISTOGRAM=25, EXPOSURE=26, COLOR4=27, COLOR16=28, COLOR64=29,
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
-           BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44, TRI_MATERIAL_CENSUS=45)
+           BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44, TRI_MATERIAL_CENSUS=45,
+           EMITTER_TRIS=46, EMITTER_WEIGHTS=47, EMITTER_CDF=48, PT_Q3_BETA=49)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
@@ -208,6 +209,10 @@ SIGNATURES = {
     "rt_time_mesh_set": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "rt_set_geometry_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_get_geometry_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_set_emitter_sampling": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "rt_get_emitter_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "rt_emitter_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "rt_emitter_select": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rt_set_triangle_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rt_reset_triangle_materials": (C.c_int, [C.c_void_p]),
     "rt_material_classes": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -267,7 +272,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
                  extra: str = "", max_size=(3840, 2160), camera_file: str | None = None, min_size=(640, 480),
                  target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None,
                  geometry_motion: bool | None = None, max_triangles: int | None = None,
-                 max_vertices: int | None = None, texture_sets: int | None = None) -> str:
+                 max_vertices: int | None = None, texture_sets: int | None = None,
+                 emitter_sampling: bool | None = None, emitter_probability: float | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
@@ -278,7 +284,9 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
     `max_triangles` / `max_vertices`: [scene] maxTriangles / maxVertices, the capacity of set_mesh
     (None: the keys are not written, the capacity is the init mesh).
     `texture_sets`: [scene] textureSets, the texture sets the context holds (None: the key is not
-    written, one set)."""
+    written, one set).
+    `emitter_sampling` / `emitter_probability`: [render] emitterSampling / emitterProbability, the initial
+    state of rt_set_emitter_sampling (None: the keys are not written; off, 0.5)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -301,6 +309,10 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
         f.write("\n[render]\nspp = %d\n" % spp)
         if geometry_motion is not None:
             f.write("geometryMotion = %s\n" % ("true" if geometry_motion else "false"))
+        if emitter_sampling is not None:
+            f.write("emitterSampling = %s\n" % ("true" if emitter_sampling else "false"))
+        if emitter_probability is not None:
+            f.write("emitterProbability = %r\n" % float(emitter_probability))
         f.write(extra)
         if tuning is None:
             tuning = tuning_from_env()
@@ -492,6 +504,21 @@ class RayTracer:
     @geometry_motion.setter
     def geometry_motion(self, on: bool):
         self._check(self.lib.rt_set_geometry_motion(self.h, 1 if on else 0), "rt_set_geometry_motion")
+
+    # ---- emitter sampling (rt_set_emitter_sampling, include/rtx_amd.h)
+    def set_emitter_sampling(self, on: bool, probability: float = 0.5):
+        """Next-event estimation of the emissive triangles of a custom material table: a diffuse
+        interaction's light sample goes to an emitter with `probability`, else to the sun or sky.  Takes
+        effect from the next LBVH build; download("EMITTER_TRIS" / "EMITTER_WEIGHTS" / "EMITTER_CDF")
+        return the list of the last build."""
+        self._check(self.lib.rt_set_emitter_sampling(self.h, 1 if on else 0, float(probability)), "rt_set_emitter_sampling")
+
+    @property
+    def emitter_sampling(self):
+        """(on, probability) of rt_get_emitter_sampling."""
+        on, q = C.c_int(), C.c_float()
+        self._check(self.lib.rt_get_emitter_sampling(self.h, C.byref(on), C.byref(q)), "rt_get_emitter_sampling")
+        return bool(on.value), q.value
 
     # ---- per-triangle materials (rt_set_triangle_materials, include/rtx_amd.h)
     def set_triangle_materials(self, ids: np.ndarray, first: int = 0):
@@ -749,6 +776,8 @@ class RayTracer:
                 raise ValueError("download: set applies to TEX_ALBEDO_AO / TEX_NORMAL_ROUGHNESS, as a small positive index")
             what |= int(set) << 8
         n = self.lib.rt_array_bytes(self.h, what)
+        if n == 0 and name.startswith("EMITTER_"):  # an empty emitter list, or none
+            return np.empty(0, dtype=dtype)
         buf = np.empty(n, dtype=np.uint8)
         self._check(self.lib.rt_download(self.h, what, buf.ctypes.data, n), "rt_download(%s)" % name)
         return buf.view(dtype)
@@ -803,6 +832,30 @@ def material_classes(ids) -> int:
     if rc != RT_OK:
         raise RtError("rt_material_classes: %s" % ERRORS.get(rc, rc))
     return c.value
+
+
+def emitter_weight(xyz, emission) -> np.float32:
+    """rt_emitter_weight: the emitter list's weight of the triangle xyz = v0 | v1 | v2 (9 floats) under
+    `emission` (3 floats), as the device computes it in fp32.  Host only."""
+    a = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1)
+    e = np.ascontiguousarray(emission, dtype=np.float32).reshape(-1)
+    if a.size != 9 or e.size != 3:
+        raise ValueError("emitter_weight: nine position floats and three emission floats")
+    w = C.c_float()
+    rc = load_library().rt_emitter_weight(a.ctypes.data, e.ctypes.data, C.byref(w))
+    if rc != RT_OK:
+        raise RtError("rt_emitter_weight: %s" % ERRORS.get(rc, rc))
+    return np.float32(w.value)
+
+
+def emitter_select(cdf, r: float):
+    """rt_emitter_select: (slot, prob) that r in [0, 1) selects from an inclusive float32 CDF.  Host only."""
+    a = np.ascontiguousarray(cdf, dtype=np.float32).reshape(-1)
+    slot, prob = C.c_uint32(), C.c_float()
+    rc = load_library().rt_emitter_select(a.ctypes.data if a.size else None, a.size, float(r), C.byref(slot), C.byref(prob))
+    if rc != RT_OK:
+        raise RtError("rt_emitter_select: %s" % ERRORS.get(rc, rc))
+    return slot.value, np.float32(prob.value)
 
 
 def default_material(id: int) -> Material:
