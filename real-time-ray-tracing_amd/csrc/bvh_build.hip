@@ -220,7 +220,7 @@ RT_DEV void radix_sort(Lds<kThr>& s) {
                 }
             }
             const uint64_t m = ((uint64_t)mhi << 32) | mlo;
-            rank[j] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            rank[j] = lane_rank(m);  // m: the lanes with this lane's digit
             if (rank[j] == 0) hist[d[j] * 16 + w + j * kW] = (uint16_t)__popcll(m);
         }
         __syncthreads();

@@ -23,10 +23,6 @@ using namespace rtd;
 
 namespace {
 
-RT_DEV uint32_t em_lane_rank(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 __global__ __launch_bounds__(256) void k_em_weigh(EmitterListParams P) {
     __shared__ uint32_t waveCount[4];
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;  // < cdfLen: the grid is cdfLen / 256
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(256) void k_em_scatter(EmitterListParams P) {
     if ((threadIdx.x & 63u) == 0u) waveCount[wave] = (uint32_t)__popcll(m);
     __syncthreads();
     if (!emits) return;
-    uint32_t slot = P.blockCount[blockIdx.x] + em_lane_rank(m);
+    uint32_t slot = P.blockCount[blockIdx.x] + lane_rank(m);
     for (uint32_t k = 0; k < wave; ++k) slot += waveCount[k];
     // slot < count <= triCount: the offsets are the counts of the same weights
     P.tris[slot] = t;

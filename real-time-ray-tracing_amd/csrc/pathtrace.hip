@@ -24,9 +24,8 @@
 #include "emitter_kernels.h"
 #include "frame_kernels.h"
 #include "pt_common.h"
-#include "queue_fetch.h"
+#include "queue_trace.h"
 #include "shade.h"
-#include "traverse.h"
 
 using namespace rtd;
 
@@ -471,18 +470,6 @@ RT_DEV uint2 pack_h4(float a, float b, float c, uint32_t d16) {
 // the same real number and so the same correctly rounded result; the division otherwise
 RT_DEV F3 div_spp(const PathTraceParams& P, F3 v) { return P.invSpp != 0.0f ? v * P.invSpp : v / (float)P.spp; }
 
-// wave sum of a per-lane count into a counter: one atomic per wave (every lane of the wave calls)
-RT_DEV void wave_add(uint32_t v, uint32_t* dst) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (__lane_id() == 0 && v) atomicAdd(dst, v);
-}
-
-// set bits of the wave mask m below this lane (v_mbcnt: no per-lane 64-bit mask kept live)
-RT_DEV uint32_t lane_rank(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 // wave-aggregated append: one atomic per wave, slots in lane order
 RT_DEV uint32_t wave_append(bool want, uint32_t* counter) {
     const unsigned long long m = __ballot(want);
@@ -509,8 +496,6 @@ RT_DEV void enqueue(const PtQueue& q, uint32_t slot, const PathVars& v, uint32_t
     q.st1[slot] = make_float4(v.beta1.x, v.beta1.y, v.beta1.z, rs.rayConeSpread);
     q.st2[slot] = make_float4(v.beta0.x, v.beta0.y, v.beta0.z, 0.0f);
 }
-
-RT_DEV SceneView scene_of(const PathTraceParams& P) { return scene_view(P.nodes, P.tlasNodes, P.triPos, P.triNrm); }
 
 // workgroup sum of traced rays into the frame counter (one atomic per workgroup)
 // w: the calling wave's index in the workgroup (wave-uniform); the lane comes from v_mbcnt, so a
@@ -646,7 +631,7 @@ __global__ __launch_bounds__(256, kOneRound ? 6 : 4) void k_pt_camera(PathTraceP
                 camV += st.visits;
                 camT += st.tests;
             }
-            rec = make_float4(st.t, __uint_as_float((uint32_t)st.hitIdx), st.hitU, st.hitV);
+            rec = hit_record(st);
             recErr = st.hitErrT;
             if (rounds > 1) {  // several rounds: the pixel's status is not known yet
                 P.ws.hit0Rec[(size_t)s * plane + pl] = rec;
@@ -1209,8 +1194,9 @@ constexpr bool kChainStaticFirst = RTX_CHAIN_STATIC != 0;  // ablation: static f
 // rays those produced, while other waves are still in their queue-3 tails; the launch ends on
 // the wave whose chain is longest, not on the sum of two tails.
 //
-//   phase 1  k_trace_queue<3>'s refilling traversal loop (same Fetch), plus a per-wave list of
-//            the reserves [lo, hi) the wave took; every entry of a reserve is traced by its lanes.
+//   phase 1  k_trace_queue<3>'s refilling traversal loop (queue_trace, same Fetch), whose top-up adds
+//            each reserve [lo, hi) the wave takes to a per-wave list and stops taking when the list
+//            is full; every entry of a reserve is traced by its lanes.
 //   phase 2  (every lane idle) the wave resumes its reserves 64 entries at a time — resume<3> —
 //            appends the I4 rays to queue 4 and to a per-wave slot list, and once 64 slots could
 //            overflow, or at the end, traces them one per lane and finishes them (resume<4>).
@@ -1220,7 +1206,7 @@ constexpr bool kChainStaticFirst = RTX_CHAIN_STATIC != 0;  // ablation: static f
 // (a workgroup-scope fence orders them), so no record crosses workgroups inside the launch.
 template <bool kStats>
 RT_DEV bool chain_step(const SceneView& sc, const TravRay& r, TravState& s, TravRec& rec, uint2* stk) {
-    return trav_step<16, false, kStats>(sc, r, s, rec, stk, 256, nullptr);  // no carried record: 168 VGPRs, no scratch
+    return trav_step<16, false, kStats>(sc, r, s, rec, stk, 256, nullptr);  // no carried record: 154 VGPRs, no scratch
 }
 
 #ifndef RTX_CHAIN_WAVES
@@ -1240,7 +1226,6 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
     const uint32_t n = P.ws.counters[kCntQ3];
     const SceneView sc = scene_of(P);
     const PtQueue& q = P.ws.q3;
-    const uint32_t allParts = (1u << kParts) - 1u;
     Fetch f;
     fetch_init(f, n, gridDim.x * 4u, blockIdx.x * 4u + (uint32_t)w, kChainStaticFirst);
     uint32_t rays = 0, rsD = 0;
@@ -1252,19 +1237,9 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
             if (lane == 0) ranges[w][0] = make_uint2(f.resLo, f.resHi);
             nRanges = 1;
         }
-        bool active = false, exhausted = false, occlusion = false;
-        uint32_t idx = 0;
-        TravRay r;
-        TravState s;
-        TravRec rec;  // scratch of chain_step (each iteration loads its own record)
-        r.org = f3(0.0f);
-        trav_init(s, sc.root);
-#pragma unroll 1
-        while (true) {
-            const unsigned long long need = __ballot(!active && !exhausted);
-            const unsigned long long busy = __ballot(active);
-            if (need != 0ull && (__popcll(need) >= kRefillMin || busy == 0ull)) {
-                const uint32_t k = (uint32_t)__popcll(need);
+        queue_trace<kStats, false, false>(  // no carried record, one step per trip: no scratch at 3 waves/SIMD
+            sc, f, stk + tid, 256,
+            [&] {  // every reserve taken goes on the list; a full list takes no more
                 if (f.resLo == f.resHi && nRanges < (uint32_t)kChainRanges) {
                     fetch_topup(f, n, P.ws.fetch, lane);
                     if (f.resLo < f.resHi) {
@@ -1272,47 +1247,26 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
                         ++nRanges;
                     }
                 }
-                const uint32_t avail = f.resHi - f.resLo;
-                const bool none = avail == 0u;  // drained, or the reserve list is full
-                if (!active && !exhausted) {
-                    const uint32_t rank = lane_rank(need);
-                    if (rank < avail) {
-                        idx = f.resLo + rank;
-                        const float4 o = q.rayO[idx], d = q.rayD[idx];
-                        trav_setup(sc, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), r);
-                        trav_init(s, sc.root);
-                        active = true;
-                        occlusion = (__float_as_uint(d.w) & kQShadowFlag) != 0u;
-                    } else if (none) {
-                        exhausted = true;
-                    }
+            },
+            [&] { return fetch_drained(f) || nRanges >= (uint32_t)kChainRanges; },
+            [&](uint32_t idx, TravRay& r) {
+                const float4 o = q.rayO[idx], d = q.rayD[idx];
+                trav_setup(sc, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), r);
+                return (__float_as_uint(d.w) & kQShadowFlag) != 0u;
+            },
+            [&](uint32_t idx, const TravState& s) {
+                P.ws.hitRec[idx] = hit_record(s);
+                P.ws.hitErr[idx] = s.hitErrT;
+                if (P.statsOut) {
+                    const uint32_t p = __float_as_uint(q.rayO[idx].w);
+                    atomicAdd(&P.statsOut[p].y, s.visits);
+                    atomicAdd(&P.statsOut[p].z, s.tests);
+                    atomicMax(&P.ws.counters[kCntMaxIter3], s.iters);
+                    atomicAdd(&P.ws.counters[kCntVisQ3], s.visits);  // detail launches only
+                    atomicAdd(&P.ws.counters[kCntTstQ3], s.tests);
                 }
-                f.resLo += k < avail ? k : avail;
-            }
-            if (__ballot(active) == 0ull) break;
-            // tail (no lane can be refilled: queue drained or reserve list full): plain per-lane
-            // loop, as in k_trace_queue
-            const bool tail = f.resLo == f.resHi && (f.drained == allParts || nRanges >= (uint32_t)kChainRanges);
-            if (tail ? active : trav_lane_steps(active, s)) {
-                bool done = false;
-                do {
-                    done = chain_step<kStats>(sc, r, s, rec, stk + tid) || s.iters >= 1024u || (occlusion && s.hitIdx >= 0);
-                } while (tail && !done);
-                if (done) {
-                    P.ws.hitRec[idx] = make_float4(s.t, __uint_as_float((uint32_t)s.hitIdx), s.hitU, s.hitV);
-                    P.ws.hitErr[idx] = s.hitErrT;
-                    if (P.statsOut) {
-                        const uint32_t p = __float_as_uint(q.rayO[idx].w);
-                        atomicAdd(&P.statsOut[p].y, s.visits);
-                        atomicAdd(&P.statsOut[p].z, s.tests);
-                        atomicMax(&P.ws.counters[kCntMaxIter3], s.iters);
-                        atomicAdd(&P.ws.counters[kCntVisQ3], s.visits);  // detail launches only
-                        atomicAdd(&P.ws.counters[kCntTstQ3], s.tests);
-                    }
-                    active = false;
-                }
-            }
-        }
+            },
+            [](bool, bool, uint32_t, const TravState&) {});
         // ---- phase 2: resume this wave's entries, trace and finish their I4 rays
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the hit records this wave wrote
         PathCtx c = path_ctx(P, sob, P.skyTree, P.sunTree);  // the light-CDF heaps from L2: LDS holds the traversal stacks
@@ -1338,13 +1292,12 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
                 if (nq4 < 16u) {  // few rays: plain per-lane loop (no ballots, no leaf batching)
 #pragma unroll 1
                     while (act)
-                        if (chain_step<kStats>(sc, r4, s4, rec4, stk + tid) || s4.iters >= 1024u || s4.hitIdx >= 0) act = false;
+                        if (trav_done(chain_step<kStats>(sc, r4, s4, rec4, stk + tid), s4, true)) act = false;
                 } else {
 #pragma unroll 1
                     while (__ballot(act) != 0ull) {
                         if (trav_lane_steps(act, s4)) {
-                            if (chain_step<kStats>(sc, r4, s4, rec4, stk + tid) || s4.iters >= 1024u || s4.hitIdx >= 0)
-                                act = false;
+                            if (trav_done(chain_step<kStats>(sc, r4, s4, rec4, stk + tid), s4, true)) act = false;
                         }
                     }
                 }
@@ -1352,9 +1305,7 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
                     PathVars v;
                     uint32_t p = 0, smp = 0;
                     c.rays = 0;
-                    (void)resume_entry<4, false, false>(c, P.ws.q4, sc, slot,
-                                                 make_float4(s4.t, __uint_as_float((uint32_t)s4.hitIdx), s4.hitU, s4.hitV),
-                                                 s4.hitErrT, v, p, smp);
+                    (void)resume_entry<4, false, false>(c, P.ws.q4, sc, slot, hit_record(s4), s4.hitErrT, v, p, smp);
                     store_path_L(c, v, p, smp);
                     if (P.statsOut) {
                         atomicAdd(&P.statsOut[p].y, s4.visits);
@@ -1382,7 +1333,7 @@ __global__ __launch_bounds__(256, RTX_CHAIN_WAVES) void k_pt_chain(PathTracePara
             nq4 += (uint32_t)__popcll(m4);
             ++ri;
         }
-        if (f.resLo == f.resHi && f.drained == allParts) break;  // queue 3 drained
+        if (f.resLo == f.resHi && fetch_drained(f)) break;  // queue 3 drained
     }
     if (P.statsOut) wave_add(rsD, &P.ws.counters[kCntDiffRes3]);
     add_rays(P, wgRays, rays, w);

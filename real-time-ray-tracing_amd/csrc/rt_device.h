@@ -134,6 +134,18 @@ RT_DEV uint32_t xwg_arrive(uint32_t* counter) {
 // the consumer, once it has seen the complete count
 RT_DEV void xwg_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
 
+// ---- Wave64 helpers.
+// set bits of the wave mask m below this lane (v_mbcnt: no per-lane 64-bit mask kept live)
+RT_DEV uint32_t lane_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// wave sum of a per-lane count into a counter: one atomic per wave (every lane of the wave calls)
+RT_DEV void wave_add(uint32_t v, uint32_t* dst) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (__lane_id() == 0 && v) atomicAdd(dst, v);
+}
+
 // Device-side failure report to the host: a word of pinned host memory (rt_context::status, one
 // word per failure kind, bvh_kernels.h kStatus*, so a plain store suffices: no PCIe atomics), which
 // sync_streams checks after its stream synchronisations.

@@ -8,16 +8,12 @@
 // queue (one atomic per 64 rays, see Fetch) so lanes stay busy until the queue is drained
 // (Aila & Laine 2009, persistent threads with dynamic fetch).
 //
-// Each lane runs TraverseBvh (traverse.h:107-253) one iteration per trav_step call, so the
-// reference semantics — 16-entry LDS stack with dropped overflow pushes, nearer child first,
-// 1024-iteration cap — hold per ray exactly as in the inline traversal.
-//
-// Exit: a lane becomes `exhausted` once its reserve is empty and every part is drained; the
-// wave leaves the loop when no lane holds a ray, which every wave reaches because the fetch
-// counters only grow and every ray ends within 1024 iterations.
-#include "frame_kernels.h"
-#include "queue_fetch.h"
-#include "traverse.h"
+// The loop is queue_trace.h's; this file supplies where a queue entry's ray comes from, where its
+// record goes and the shading list of queue 3.  Each lane runs TraverseBvh (traverse.h:107-253)
+// one iteration per trav_step call, so the reference semantics — 16-entry LDS stack with dropped
+// overflow pushes, nearer child first, 1024-iteration cap — hold per ray exactly as in the inline
+// traversal.
+#include "queue_trace.h"
 
 using namespace rtd;
 
@@ -25,10 +21,6 @@ namespace {
 
 constexpr int kTraceBlock = 256;
 constexpr uint32_t kTrace3Short = 1u << 20;  // queue-3 length below which trace3ShortBlocks apply
-#ifndef RTX_LEAF_BATCH
-#define RTX_LEAF_BATCH 1
-#endif
-constexpr bool kLeafBatch = RTX_LEAF_BATCH != 0;  // ablation: -DRTX_LEAF_BATCH=0
 
 // A wave's pending entries of the shading list (PtWorkspace::shade3) go out n <= 64 at a time: one
 // atomic per flush, and the wave waits for its return once per ~64 listed entries.  (One atomic per
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
     const PtQueue& q = kStep == 3 ? P.ws.q3 : P.ws.q4;
     const uint32_t n = P.ws.counters[kStep == 3 ? kCntQ3 : kCntQ4];
     uint32_t* fetchCounters = P.ws.fetch + (kStep == 3 ? 0 : kParts * 16);
-    const SceneView sc = scene_view(P.nodes, P.tlasNodes, P.triPos, P.triNrm);
+    const SceneView sc = scene_of(P);
 
     // a short queue 3 runs on the first trace3ShortBlocks workgroups only (frame.cpp); the others
     // leave before taking any work, and the static first batches are cut over the ones that stay
@@ -80,101 +72,52 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_queue(PathTraceParams P) 
     Fetch f;
     fetch_init(f, n, blocks * wavesPerBlock, blockIdx.x * wavesPerBlock + (uint32_t)(tid >> 6));
 
-    bool active = false, exhausted = false, occlusion = false;
-    uint32_t idx = 0, accV = 0, accT = 0;
+    uint32_t accV = 0, accT = 0;
     uint32_t* const shl = shadeList + (kStep == 3 ? (tid & ~63) : 0);  // this wave's
     uint32_t nList = 0;  // wave-uniform
-    TravRay r;
-    TravState s;
-    TravRec rec;  // the record the lane's next iteration processes
-    r.org = f3(0.0f);
-    trav_init(s, sc.root);
-#pragma unroll 1
-    while (true) {
-        const unsigned long long need = __ballot(!active && !exhausted);
-        const unsigned long long busy = __ballot(active);
-        if (need != 0ull && (__popcll(need) >= kRefillMin || busy == 0ull)) {
-            const uint32_t k = (uint32_t)__popcll(need);
-            fetch_topup(f, n, fetchCounters, lane);
-            const uint32_t avail = f.resHi - f.resLo;
-            const bool none = avail == 0u && f.drained == (1u << kParts) - 1u;
-            if (!active && !exhausted) {
-                const uint32_t rank = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-                if (rank < avail) {
-                    idx = f.resLo + rank;
-                    const float4 o = q.rayO[idx], d = q.rayD[idx];
-                    trav_setup(sc, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), r);
-                    trav_init(s, sc.root);
-                    rec = trav_first_rec(sc);
-                    active = true;
-                    occlusion = (kStep == 4 && !kClosest) || (__float_as_uint(d.w) & kQShadowFlag) != 0u;
-                    if constexpr (kNee) occlusion = occlusion && (__float_as_uint(d.w) & kQEmitterFlag) == 0u;
-                } else if (none) {
-                    exhausted = true;
-                }
+    queue_trace<kStats, true, true>(
+        sc, f, stk + tid, kTraceBlock,
+        [&] { fetch_topup(f, n, fetchCounters, lane); },
+        [&] { return fetch_drained(f); },
+        [&](uint32_t idx, TravRay& r) {
+            const float4 o = q.rayO[idx], d = q.rayD[idx];
+            trav_setup(sc, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), r);
+            bool occlusion = (kStep == 4 && !kClosest) || (__float_as_uint(d.w) & kQShadowFlag) != 0u;
+            if constexpr (kNee) occlusion = occlusion && (__float_as_uint(d.w) & kQEmitterFlag) == 0u;
+            return occlusion;
+        },
+        [&](uint32_t idx, const TravState& s) {
+            (kStep == 3 ? P.ws.hitRec : P.ws.hitRec4)[idx] = hit_record(s);
+            (kStep == 3 ? P.ws.hitErr : P.ws.hitErr4)[idx] = s.hitErrT;
+            if (P.ws.itersOut) P.ws.itersOut[idx] = s.iters;
+            if (P.statsOut) {
+                const uint32_t p = __float_as_uint(q.rayO[idx].w);
+                atomicAdd(&P.statsOut[p].y, s.visits);
+                atomicAdd(&P.statsOut[p].z, s.tests);
+                atomicMax(&P.ws.counters[kStep == 3 ? kCntMaxIter3 : kCntMaxIter4], s.iters);
+                accV += s.visits;
+                accT += s.tests;
             }
-            f.resLo += k < avail ? k : avail;
-        }
-        if (__ballot(active) == 0ull) break;
-        // Tail: this wave's reserve is empty and every part drained, so no lane can be refilled.
-        // The remaining rays then run in a plain per-lane loop, without the refill ballots and the
-        // leaf batching (a wave in the tail has few lanes left, and its iteration latency is the
-        // kernel's tail).  Each ray's steps are unchanged.
-        const bool tail = f.resLo == f.resHi && f.drained == (1u << kParts) - 1u;
-        bool fin = false;  // this lane finished its ray in this trip
-        if (tail || !kLeafBatch ? active : trav_lane_steps(active, s)) {
-            bool done;
-            do {  // two steps per trip: the loop's refill / exec-mask bookkeeping once per two
-                done = trav_step<16, true, kStats>(sc, r, s, rec, stk + tid, kTraceBlock, nullptr) || s.iters >= 1024u ||
-                       (occlusion && s.hitIdx >= 0);
-                if (!done && (tail || !kLeafBatch || trav_lane_steps(true, s)))
-                    done = trav_step<16, true, kStats>(sc, r, s, rec, stk + tid, kTraceBlock, nullptr) || s.iters >= 1024u ||
-                           (occlusion && s.hitIdx >= 0);
-            } while (tail && !done);
-            if (done) {
-                (kStep == 3 ? P.ws.hitRec : P.ws.hitRec4)[idx] =
-                    make_float4(s.t, __uint_as_float((uint32_t)s.hitIdx), s.hitU, s.hitV);
-                (kStep == 3 ? P.ws.hitErr : P.ws.hitErr4)[idx] = s.hitErrT;
-                if (P.ws.itersOut) P.ws.itersOut[idx] = s.iters;
-                if (P.statsOut) {
-                    const uint32_t p = __float_as_uint(q.rayO[idx].w);
-                    atomicAdd(&P.statsOut[p].y, s.visits);
-                    atomicAdd(&P.statsOut[p].z, s.tests);
-                    atomicMax(&P.ws.counters[kStep == 3 ? kCntMaxIter3 : kCntMaxIter4], s.iters);
-                    accV += s.visits;
-                    accT += s.tests;
-                }
-                active = false;
-                fin = true;
-            }
-        }
+        },
         // the entries whose resume may shade go to the shading list (split resume<3>); wave-uniform flow
-        if (kStep == 3 && P.ws.shade3) {
-            const unsigned long long m = __ballot(fin && q3_shades(occlusion ? kQShadowFlag : 0u, (uint32_t)s.hitIdx));
-            if (m != 0ull) {
-                const uint32_t k = (uint32_t)__popcll(m);
-                if (nList + k > 64u) {
-                    flush_shade_list(P, shl, nList, lane);
-                    nList = 0u;
+        [&](bool fin, bool occlusion, uint32_t idx, const TravState& s) {
+            if (kStep == 3 && P.ws.shade3) {
+                const unsigned long long m = __ballot(fin && q3_shades(occlusion ? kQShadowFlag : 0u, (uint32_t)s.hitIdx));
+                if (m != 0ull) {
+                    const uint32_t k = (uint32_t)__popcll(m);
+                    if (nList + k > 64u) {
+                        flush_shade_list(P, shl, nList, lane);
+                        nList = 0u;
+                    }
+                    if ((m >> lane) & 1ull) shl[nList + lane_rank(m)] = idx;
+                    nList += k;
                 }
-                if ((m >> lane) & 1ull)
-                    shl[nList + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = idx;
-                nList += k;
             }
-        }
-    }
+        });
     if (kStep == 3 && P.ws.shade3 && nList) flush_shade_list(P, shl, nList, lane);
-    if (P.statsOut) {  // every lane left the loop together (the wave-uniform break above)
-        uint32_t v = accV, t = accT;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            v += __shfl_xor(v, o);
-            t += __shfl_xor(t, o);
-        }
-        if (lane == 0) {
-            if (v) atomicAdd(&P.ws.counters[kStep == 3 ? kCntVisQ3 : kCntVisQ4], v);
-            if (t) atomicAdd(&P.ws.counters[kStep == 3 ? kCntTstQ3 : kCntTstQ4], t);
-        }
+    if (P.statsOut) {  // every lane left the loop together
+        wave_add(accV, &P.ws.counters[kStep == 3 ? kCntVisQ3 : kCntVisQ4]);
+        wave_add(accT, &P.ws.counters[kStep == 3 ? kCntTstQ3 : kCntTstQ4]);
     }
 }
 

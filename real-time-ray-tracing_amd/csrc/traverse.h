@@ -459,6 +459,15 @@ RT_DEV bool trav_lane_steps(bool active, const TravState& s) {
     return active && (!atLeaf || doLeaf);
 }
 
+// Whether a ray's traversal ends with the trav_step call that returned stackEmpty: the stack ran
+// empty, the reference's 1024-iteration cap, or (firstHit: occlusion and any-hit rays) a hit is recorded.
+RT_DEV bool trav_done(bool stackEmpty, const TravState& s, bool firstHit) {
+    return stackEmpty || s.iters >= 1024u || (firstHit && s.hitIdx >= 0);
+}
+
+// the 16-B hit record of a finished traversal: t, triangle index (-1: none), u, v
+RT_DEV float4 hit_record(const TravState& s) { return make_float4(s.t, __uint_as_float((uint32_t)s.hitIdx), s.hitU, s.hitV); }
+
 // hit finalisation (traverse.h:161-174, traverse.cuh:192-217), once for the closest hit
 RT_DEV void finalize_hit(const SceneView& sc, F3 org, F3 dir, float t, int hitIdx, float hitU, float hitV,
                          float hitErrT, HitInfo& out) {

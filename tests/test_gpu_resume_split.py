@@ -121,6 +121,37 @@ def test_chain_and_four_kernels_agree_on_detail_counts(rtx, oracle, tmp_path, w,
     assert rays0 == int(g0["rays"].sum())
 
 
+def test_frame_tracers_dynamic_fetch_agrees_and_matches_oracle(rtx, oracle, tmp_path, default_scene, sky_tex):
+    """The frame tracers' dynamic fetch.  At the other tests' sizes the static first batches
+    (cus x tracePerCu x 256 entries) take all of queue 3; here one workgroup per CU ([tuning]
+    tracePerCu = 1) leaves queue 3 longer than those batches plus one 64-entry reserve per fetch part,
+    so k_trace_queue<3> (unsplit, and split with its shading list) and the chain's phase 1, which
+    fetches every entry, run the refilling loop's top-ups, ragged part ends and tail.  The three agree
+    on everything a detail launch counts, and with the CPU oracle bit for bit."""
+    import torch
+
+    w, h, spp = 320, 180, 4
+    ocam, rcam = terrain_camera(rtx, oracle, w, h)
+    variants = [("chain", {"chain": "always"}), ("unsplit", {"chain": "off", "resumeSplit": 0}),
+                ("split", {"chain": "off", "resumeSplit": 1})]
+    (g0, q0, rays0, st0), unsplit, split = (launch(rtx, tmp_path, name, w, h, spp, dict(tuning, tracePerCu=1), rcam)
+                                            for name, tuning in variants)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print("queue 3: %d entries, %d CUs" % (q0[0], cus))
+    assert q0[0] > cus * 256 + 8 * 64, (q0[0], cus)
+    for g, q, rays, st in (unsplit, split):
+        assert_gbuffers_equal(g, g0)  # RAYS among them
+        assert rays == rays0
+        for k in (0, 1, 4, 11, 20, 21):
+            assert q[k] == q0[k], k
+    for q in (q0, unsplit[1], split[1]):
+        assert q[10] == 0  # kCntError
+    s, tex = sky_tex
+    o = oracle.pathtrace(default_scene["bvh"], w, h, frame_num=FRAME, spp=spp, cam=ocam, sky_out=s, tex=tex)
+    assert_gbuffers_equal(g0, o)
+    assert rays0 == int(o["rays"].sum())
+
+
 def test_emissive_override_finishes_without_shading(rtx, oracle, tmp_path, default_scene, sky_tex):
     """materialOverride = 0 (emissive): no entry may shade.  The override covers every triangle, so a
     camera ray's hit already ends its path (hitLight) and nothing reaches queue 3: the shading list
