@@ -16,6 +16,7 @@
 //   scaled      uint2  = half4 at screen size, rgba uint32 = RGBA8
 #include "gaussian_tables.h"
 #include "frame_kernels.h"
+#include "launch.h"
 #include "pt_common.h"
 #include "rt_device.h"
 #include "rtmath.h"
@@ -1734,46 +1735,46 @@ __global__ __launch_bounds__(256) void k_hdr_out(const uint2* color, float4* hdr
 
 }  // namespace
 
-// the list chain's first two a-trous passes: depth-weight reciprocal x paired tap weights
-template <int S, bool kRedirect, bool kAlbedo = false, bool kCopy = false>
-static void launch_s5_list(bool rcp, bool pk, dim3 g, hipStream_t s, const DenoisePostParams& Q, const uint2* in,
-                           uint2* out, const uint2* alt) {
-    if (kDnSplit && Q.listSplit) {  // two threads per pixel (spatial5_tile_split)
-        const dim3 b2(512);
-        if (rcp && pk) hipLaunchKernelGGL((k_spatial5_list2<S, true, kRedirect, true, kAlbedo, kCopy>), g, b2, 0, s, Q, in, out, alt);
-        else if (rcp) hipLaunchKernelGGL((k_spatial5_list2<S, true, kRedirect, false, kAlbedo, kCopy>), g, b2, 0, s, Q, in, out, alt);
-        else if (pk) hipLaunchKernelGGL((k_spatial5_list2<S, false, kRedirect, true, kAlbedo, kCopy>), g, b2, 0, s, Q, in, out, alt);
-        else hipLaunchKernelGGL((k_spatial5_list2<S, false, kRedirect, false, kAlbedo, kCopy>), g, b2, 0, s, Q, in, out, alt);
-        return;
-    }
-    const dim3 b(256);
-    if (rcp && pk) hipLaunchKernelGGL((k_spatial5_list<S, true, kRedirect, true, kAlbedo, kCopy>), g, b, 0, s, Q, in, out, alt);
-    else if (rcp) hipLaunchKernelGGL((k_spatial5_list<S, true, kRedirect, false, kAlbedo, kCopy>), g, b, 0, s, Q, in, out, alt);
-    else if (pk) hipLaunchKernelGGL((k_spatial5_list<S, false, kRedirect, true, kAlbedo, kCopy>), g, b, 0, s, Q, in, out, alt);
-    else hipLaunchKernelGGL((k_spatial5_list<S, false, kRedirect, false, kAlbedo, kCopy>), g, b, 0, s, Q, in, out, alt);
+// ---- Host side.  A pass picks its kernel instantiation from run-time settings through
+// rtl::with_flags (launch.h); each kernel template is named in one launch expression.
+
+#define DN_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
+
+namespace {
+
+// HIP events around denoise kernel k (P->marks: bench.py's per-kernel split of whole frames)
+hipError_t dn_mark(const DenoisePostParams* P, int k, int end, hipStream_t s) {
+    if (!P->marks || !P->marks[2 * k + end]) return hipSuccess;
+    return hipEventRecord(P->marks[2 * k + end], s);
 }
+
+// one launch between the marks pair of denoise kernel `mark` (kNoMark: a kernel without one)
+constexpr int kNoMark = -1;
+template <class Kernel, class... Args>
+hipError_t dn_launch(const DenoisePostParams* P, int mark, hipStream_t s, Kernel kernel, dim3 g, dim3 b,
+                     Args&&... args) {
+    if (mark != kNoMark) DN_TRY(dn_mark(P, mark, 0, s));
+    DN_TRY(rtl::launch(kernel, g, b, s, args...));
+    return mark != kNoMark ? dn_mark(P, mark, 1, s) : hipSuccess;
+}
+
+const dim3 b256(256), b512(512);
 
 // k_scale_post's footprint of 18 screen texels along an axis spans at most 17 * r + 5 render
 // texels (r = render / screen: the first tap one before t1, the last two after, one more for the
 // floors' rounding); the small LDS tile holds 24 of them
-static bool scale_lds_small(int render, int screen) { return 17 * render + 5 * screen <= 24 * screen - screen; }
+bool scale_lds_small(int render, int screen) { return 17 * render + 5 * screen <= 24 * screen - screen; }
 
-#define LAUNCH_CHECK()                          \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return e__;      \
-    } while (0)
+// the paired tap weights need a filter's sigma_normal finite and > 0 (rtpk::pow_pos_ok, device only)
+bool pk_ok(float sigma_normal) { return kDnPk && sigma_normal > 0.0f && sigma_normal < __builtin_inff(); }
 
-// HIP events around denoise kernel k (P->marks: bench.py's per-kernel split of whole frames)
-static hipError_t dn_mark(const DenoisePostParams* P, int k, int end, hipStream_t s) {
-    if (!P->marks || !P->marks[2 * k + end]) return hipSuccess;
-    return hipEventRecord(P->marks[2 * k + end], s);
-}
-#define DN_MARK(k, end)                                                 \
-    do {                                                                \
-        hipError_t e__ = dn_mark(P, (k), (end), s);                     \
-        if (e__ != hipSuccess) return e__;                              \
-    } while (0)
+// the sizes of the DownScale4 levels
+struct Levels {
+    int W4, H4, W16, H16, W64, H64;
+    explicit Levels(const DenoisePostParams* P)
+        : W4(((int)P->W + 3) / 4), H4(((int)P->H + 3) / 4), W16((W4 + 3) / 4), H16((H4 + 3) / 4), W64((W16 + 3) / 4),
+          H64((H16 + 3) / 4) {}
+};
 
 // Tile rows of each pass.  The full frame computes every tile; a strip-local denoise (multi-GPU,
 // rows [rowA, rowB) in 64-row blocks) computes each pass only on the rows the passes after it
@@ -1786,7 +1787,6 @@ static hipError_t dn_mark(const DenoisePostParams* P, int k, int end, hipStream_
 //   TemporalFilter (+ noise)    [A-4, B+4)
 // The accumulation / history rows of the strip itself and the histogram counts are exchanged
 // between the ranks afterwards (rt_set_collective_hook).
-namespace {
 void tile_range(const DenoisePostParams* P, int halo, int& t0, int& t1) {
     const int H16 = ((int)P->H + 15) / 16;
     if (!P->stripLocal) { t0 = 0; t1 = H16; return; }
@@ -1795,83 +1795,70 @@ void tile_range(const DenoisePostParams* P, int halo, int& t0, int& t1) {
     t0 = t0 < 0 ? 0 : t0;
     t1 = t1 > H16 ? H16 : t1;
 }
-}  // namespace
 
-// phase 0: TemporalSpatialDenoising + DownScale4 + Histogram2 (the histogram is this strip's share
-// when strip-local); phase 1: AutoExposure onwards.  A multi-GPU host sums the histograms between
-// the phases.
-static hipError_t denoise_phase3(DenoisePostParams* P, hipStream_t s);
+// a copy of the parameters and the grid for the launch of tile rows [t0, t1) (halo tiles around
+// the strip); false when there are none
+bool tiles(const DenoisePostParams* P, int halo, DenoisePostParams& Q, dim3& g) {
+    int t0, t1;
+    tile_range(P, halo, t0, t1);
+    Q = *P;
+    Q.ty0 = t0;
+    Q.ty1 = t1;
+    g = dim3(((unsigned)P->W + 15) / 16, (unsigned)(t1 > t0 ? t1 - t0 : 0));
+    return t1 > t0;
+}
 
-extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* P, hipStream_t s, int phase) {
-    if (phase == 3) return denoise_phase3(P, s);
-    const int W = (int)P->W, H = (int)P->H, Ws = (int)P->Ws, Hs = (int)P->Hs;
+// the tile noise levels of `cur` as kernels of their own (a pass's epilogue computes them otherwise)
+hipError_t launch_noise(const DenoisePostParams* P, hipStream_t s, uint2* cur, int level) {
+    const int W = (int)P->W, H = (int)P->H;
+    const int W8 = (W + 7) / 8, H8 = (H + 7) / 8, W16 = (W + 15) / 16, H16 = (H + 15) / 16;
+    DN_TRY(dn_launch(P, kNoMark, s, k_tile_noise, dim3((W8 * H8 + 7) / 8), b256, *P, cur));
+    DN_TRY(dn_launch(P, kNoMark, s, k_noise16, dim3((W16 * H16 + 255) / 256), b256, *P));
+    if (P->visualize) {
+        DenoisePostParams V = *P;
+        V.ty0 = 0;
+        V.ty1 = H16;
+        DN_TRY(dn_launch(P, kNoMark, s, k_noise_visualize, dim3(W16, H16), b256, V, cur, level));
+    }
+    return hipSuccess;
+}
+
+// How the a-trous passes run: over list 1 (at one or two threads per pixel; folded: the first pass
+// also finishes the tiles off list 1 for the last, which then runs over the list with ApplyAlbedo in
+// its store) or over the frame; the depth weights' divisor as a reciprocal; paired tap weights.
+struct AtrousPlan {
+    bool list, split, fold, rcp, pk;
+    dim3 gList;
+};
+
+// a-trous pass S (3, 6, 12: denoise kernels 2, 3, 4) of tile rows Q.ty0 .. Q.ty1.  The last pass
+// applies the albedo; with the lists the passes after the first redirect their taps outside list 1
+// to `alt`, and the frame-wide last pass of an unfolded list chain does so too.
+template <int S>
+hipError_t launch_atrous(const DenoisePostParams* P, hipStream_t s, const AtrousPlan& c, dim3 g,
+                         const DenoisePostParams& Q, const uint2* in, uint2* out, const uint2* alt) {
+    constexpr bool kFirst = S == 3, kLast = S == 12;
+    constexpr int kMark = kFirst ? 2 : kLast ? 4 : 3;
+    if (c.list && (!kLast || c.fold))
+        return rtl::with_flags([&](auto split, auto copy, auto rcp, auto pk) {
+            constexpr bool kCopy = kFirst && copy;
+            auto k = split ? k_spatial5_list2<S, rcp, !kFirst, pk, kLast, kCopy>
+                           : k_spatial5_list<S, rcp, !kFirst, pk, kLast, kCopy>;
+            return dn_launch(P, kMark, s, k, c.gList, split ? b512 : b256, Q, in, out, alt);
+        }, c.split, c.fold, c.rcp, c.pk);
+    return rtl::with_flags([&](auto redirect, auto rcp, auto pk) {
+        constexpr bool kRedirect = kLast && redirect, kPk = kRedirect && pk;  // paired weights: list chain only
+        return dn_launch(P, kMark, s, k_spatial5<S, kLast, rcp, kRedirect, kPk>, g, b256, Q, in, out, alt);
+    }, c.list, c.rcp, c.pk);
+}
+
+// ---- TemporalSpatialDenoising (denoising.cu:51-188); out: the colour buffer it ended in, and
+// whether k_temporal already wrote the history depth
+hipError_t temporal_spatial_denoising(DenoisePostParams* P, hipStream_t s, uint2*& out, bool& histDepthDone) {
+    const int W = (int)P->W, H = (int)P->H;
     const size_t Pn = (size_t)W * H;
-    const dim3 b256(256);
-    const int W4 = (W + 3) / 4, H4 = (H + 3) / 4, W16b = (W4 + 3) / 4, H16b = (H4 + 3) / 4, W64 = (W16b + 3) / 4,
-              H64 = (H16b + 3) / 4;
-    hipError_t e;
-    // a copy of the parameters for the launch of tile rows [t0, t1) (halo tiles around the strip)
-    auto tiles = [&](int halo, DenoisePostParams& Q, dim3& g) {
-        int t0, t1;
-        tile_range(P, halo, t0, t1);
-        Q = *P;
-        Q.ty0 = t0;
-        Q.ty1 = t1;
-        g = dim3((W + 15) / 16, (unsigned)(t1 > t0 ? t1 - t0 : 0));
-        return t1 > t0;
-    };
     DenoisePostParams Q;
     dim3 g;
-    if (phase == 1) {
-        uint2* cur = P->finalColor;
-        if (P->postProcess) {
-            if (!P->exposureDone) {
-                hipLaunchKernelGGL(k_auto_exposure, dim3(1), dim3(64), 0, s, P->exposure, (const uint32_t*)P->histogram,
-                                   (float)(W64 * H64), P->deltaTime, P->gain, P->autoExposure, P->fixedExposure);
-                LAUNCH_CHECK();
-            }
-            // Bloom and LensFlare modify RenderColorBuffer, which here may be the next frame's
-            // history (TemporalFilter2's output): both write a colour buffer instead (full frame only).
-            uint2* post = cur == P->colorA ? P->colorB : P->colorA;
-            const dim3 g16((W + 15) / 16, (H + 15) / 16);
-            if (P->bloom) {
-                hipLaunchKernelGGL(k_bloom_gauss, dim3((W4 + 11) / 12, (H4 + 11) / 12), b256, 0, s, (const uint2*)P->c4,
-                                   W4, H4, P->bloom4, (const float*)P->exposure);
-                LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_bloom_gauss, dim3((W16b + 11) / 12, (H16b + 11) / 12), b256, 0, s,
-                                   (const uint2*)P->c16, W16b, H16b, P->bloom16, (const float*)P->exposure);
-                LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_bloom_apply, g16, b256, 0, s, *P, (const uint2*)cur, post);
-                LAUNCH_CHECK();
-                cur = post;
-            }
-            if (P->lensFlare) {
-                hipLaunchKernelGGL(k_lens_flare, g16, b256, 0, s, *P, (const uint2*)cur, post);
-                LAUNCH_CHECK();
-                cur = post;
-            }
-            P->finalColor = cur;
-        }
-        Q = *P;
-        Q.sharpen = P->postProcess && P->sharpen;
-        Q.tonemap = P->postProcess && P->tonemap;
-        int t0 = 0, t1 = (Hs + 15) / 16;
-        if (P->stripLocal) tile_range(P, 0, t0, t1);  // screen = render size for strips
-        Q.ty0 = t0;
-        Q.ty1 = t1;
-        if (t1 > t0) {
-            DN_MARK(7, 0);
-            const dim3 gs((Ws + 15) / 16, (unsigned)(t1 - t0));
-            if (scale_lds_small(W, Ws) && scale_lds_small(H, Hs))
-                hipLaunchKernelGGL(k_scale_post<kScaleLdsSmall>, gs, dim3(kScaleThreads), 0, s, Q, (const uint2*)cur);
-            else
-                hipLaunchKernelGGL(k_scale_post<kScaleLdsLarge>, gs, dim3(kScaleThreads), 0, s, Q, (const uint2*)cur);
-            LAUNCH_CHECK();
-            DN_MARK(7, 1);
-        }
-        P->finalScaled = P->scaledB;
-        return hipSuccess;
-    }
     // Buffer plan: the path-trace colour (colorA) and colorB ping-pong; SpatialFilter7x7 writes
     // AccumulationColorBuffer directly and TemporalFilter2 the next history buffer, so neither
     // needs the reference's copy (denoising.cu:110-112, 178-183).  The tile noise levels are
@@ -1880,22 +1867,6 @@ extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* P, hipStream_t s, int
     uint2* cur = P->colorA;
     uint2* spare = P->colorB;
     auto next_from = [&](uint2* dst) { if (cur == P->colorA || cur == P->colorB) spare = cur; cur = dst; };
-    const int W8 = (W + 7) / 8, H8 = (H + 7) / 8, W16 = (W + 15) / 16, H16 = (H + 15) / 16;
-    auto noise = [&](int level) -> hipError_t {
-        hipLaunchKernelGGL(k_tile_noise, dim3((W8 * H8 + 7) / 8), b256, 0, s, *P, (const uint2*)cur);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_noise16, dim3((W16 * H16 + 255) / 256), b256, 0, s, *P);
-        LAUNCH_CHECK();
-        if (P->visualize) {
-            DenoisePostParams V = *P;
-            V.ty0 = 0;
-            V.ty1 = H16;
-            hipLaunchKernelGGL(k_noise_visualize, dim3(W16, H16), b256, 0, s, V, cur, level);
-            LAUNCH_CHECK();
-        }
-        return hipSuccess;
-    };
-    // ---- TemporalSpatialDenoising (denoising.cu:51-188)
     // The whole chain with the tile noise levels computed in the passes' epilogues runs the
     // noise-gated passes over active-tile lists (above); rcp: the depth weights' divisor of pass k
     // as a reciprocal (DenoisePostParams::rcpDepthOk)
@@ -1903,17 +1874,19 @@ extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* P, hipStream_t s, int
     // it also writes tiles of this frame's, so the list chain writes another buffer (accumAlt): the
     // host swaps the two, or, when the accumulation buffer is the caller's (a strip-local denoise
     // exchanges it), copies the rows this chain finished back into it (frame.cpp run_denoise)
-    const bool useList = P->tileList && P->accumAlt && P->temporal && P->frameNum != 1 &&
-                         P->localSpatial && P->wideSpatial && !P->visualize;
+    const bool temporal = P->temporal && P->frameNum != 1;
+    const bool useList = P->tileList && P->accumAlt && temporal && P->localSpatial && P->wideSpatial && !P->visualize;
     uint2* const accOut = useList ? P->accumAlt : P->accum;
     P->listUsed = useList ? 1 : 0;
     const bool rcpT = (P->rcpDepthOk & 1) != 0, rcp7 = (P->rcpDepthOk & 2) != 0, rcp5 = (P->rcpDepthOk & 4) != 0;
-    const float sn5 = P->dn.large_denoise_sigma_normal;
-    const bool pk5 = kDnPk && sn5 > 0.0f && sn5 < __builtin_inff();  // rtpk::pow_pos_ok
-    const float sn7 = P->dn.local_denoise_sigma_normal;
-    const bool pk7 = kDnPk && sn7 > 0.0f && sn7 < __builtin_inff();
-    const float snT = P->dn.temporal_denoise_sigma_normal;
-    const bool pkT = kDnPk && snT > 0.0f && snT < __builtin_inff();
+    const bool pkT = pk_ok(P->dn.temporal_denoise_sigma_normal), pk7 = pk_ok(P->dn.local_denoise_sigma_normal),
+               pk5 = pk_ok(P->dn.large_denoise_sigma_normal);
+    // the list passes at two threads per pixel (spatial5_tile_split); [tuning] dnFold, and every split chain
+    const bool split = kDnSplit && P->listSplit, fold = useList && (P->listFold || split);
+    // the noise levels in the epilogue of TemporalFilter (for SpatialFilter7x7) and of SpatialFilter7x7
+    // (for the a-trous passes)
+    const bool noise1 = temporal && P->localSpatial && !P->visualize;
+    const bool noise2 = P->localSpatial && P->wideSpatial && !P->visualize;
     // one workgroup per list slot the frame can fill: the lists hold tiles of TemporalFilter's tile
     // rows only (a strip-local rank's strip and halo), a contiguous run of tile indices, so a
     // partition (tile % 16) holds at most a sixteenth of them
@@ -1922,240 +1895,196 @@ extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* P, hipStream_t s, int
     const uint32_t listRows = (uint32_t)(lt1 > lt0 ? ((lt1 - lt0) * ((W + 15) / 16) + kListParts - 1) / kListParts : 0);
     const uint32_t capRows = P->tileCap / kListParts + 1;
     const dim3 gList((unsigned)(kListParts * (listRows < capRows ? listRows : capRows)));
-    bool noise1 = false, histDepthDone = false;
-    if (P->temporal && P->frameNum != 1) {
-        noise1 = P->localSpatial && !P->visualize;
+    histDepthDone = false;
+    if (temporal) {
         uint2* dst = spare;
-        if (tiles(4, Q, g)) {
+        if (tiles(P, 4, Q, g)) {
             // the whole frame without the debug outlines (which rewrite depth): TemporalFilter2's
             // HistoryDepthBuffer copy rides on this pass's depth reads
             Q.histDepthInTemporal = histDepthDone = P->temporal2 && !P->stripLocal && !P->visualize;
-            DN_MARK(0, 0);
-            if (useList) {
-                if (rcpT && pkT) hipLaunchKernelGGL((k_temporal<true, true, true, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else if (rcpT) hipLaunchKernelGGL((k_temporal<true, true, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else if (pkT) hipLaunchKernelGGL((k_temporal<true, true, false, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_temporal<true, true, false>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-            } else if (noise1) {
-                if (rcpT) hipLaunchKernelGGL((k_temporal<true, false, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_temporal<true, false, false>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-            } else {
-                if (rcpT) hipLaunchKernelGGL((k_temporal<false, false, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_temporal<false, false, false>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-            }
-            LAUNCH_CHECK();
-            DN_MARK(0, 1);
+            DN_TRY(rtl::with_flags([&](auto noise, auto list, auto rcp, auto pk) {
+                constexpr bool kNoise = noise || list, kPk = list && pk;  // paired weights: list chain only
+                return dn_launch(P, 0, s, k_temporal<kNoise, list, rcp, kPk>, g, b256, Q, cur, dst);
+            }, noise1, useList, rcpT, pkT));
         }
         next_from(dst);
     }
-    bool noise2 = false;
     if (P->localSpatial) {
-        if (!noise1 && (e = noise(1)) != hipSuccess) return e;
-        noise2 = P->wideSpatial && !P->visualize;
+        if (!noise1) DN_TRY(launch_noise(P, s, cur, 1));
         uint2* dst = P->temporal ? accOut : spare;
-        if (tiles(3, Q, g)) {
-            DN_MARK(1, 0);
-            if (useList) {  // list 0 only; TemporalFilter wrote the other tiles into the accumulation buffer
-                const dim3 b512(512);
-                const bool split = kDnSplit && Q.listSplit;
-                if (split && rcp7 && pk7) hipLaunchKernelGGL((k_spatial7_list2<true, true>), gList, b512, 0, s, Q, (const uint2*)cur, dst);
-                else if (split && rcp7) hipLaunchKernelGGL((k_spatial7_list2<true, false>), gList, b512, 0, s, Q, (const uint2*)cur, dst);
-                else if (split && pk7) hipLaunchKernelGGL((k_spatial7_list2<false, true>), gList, b512, 0, s, Q, (const uint2*)cur, dst);
-                else if (split) hipLaunchKernelGGL((k_spatial7_list2<false, false>), gList, b512, 0, s, Q, (const uint2*)cur, dst);
-                else if (rcp7 && pk7) hipLaunchKernelGGL((k_spatial7_list<true, true>), gList, b256, 0, s, Q, (const uint2*)cur, dst);
-                else if (rcp7) hipLaunchKernelGGL((k_spatial7_list<true, false>), gList, b256, 0, s, Q, (const uint2*)cur, dst);
-                else if (pk7) hipLaunchKernelGGL((k_spatial7_list<false, true>), gList, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_spatial7_list<false, false>), gList, b256, 0, s, Q, (const uint2*)cur, dst);
-            } else if (noise2) {
-                if (rcp7) hipLaunchKernelGGL((k_spatial7<true, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_spatial7<true, false>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-            } else {
-                if (rcp7) hipLaunchKernelGGL((k_spatial7<false, true>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-                else hipLaunchKernelGGL((k_spatial7<false, false>), g, b256, 0, s, Q, (const uint2*)cur, dst);
-            }
-            LAUNCH_CHECK();
-            DN_MARK(1, 1);
+        if (tiles(P, 3, Q, g)) {
+            if (useList)  // list 0 only; TemporalFilter wrote the other tiles into the accumulation buffer
+                DN_TRY(rtl::with_flags([&](auto two, auto rcp, auto pk) {
+                    auto k = two ? k_spatial7_list2<rcp, pk> : k_spatial7_list<rcp, pk>;
+                    return dn_launch(P, 1, s, k, gList, two ? b512 : b256, Q, cur, dst);
+                }, split, rcp7, pk7));
+            else
+                DN_TRY(rtl::with_flags([&](auto noise, auto rcp) {
+                    return dn_launch(P, 1, s, k_spatial7<noise, rcp>, g, b256, Q, cur, dst);
+                }, noise2, rcp7));
         }
         next_from(dst);
     } else if (P->temporal) {
-        if ((e = hipMemcpyAsync(P->accum, cur, Pn * 8, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+        DN_TRY(hipMemcpyAsync(P->accum, cur, Pn * 8, hipMemcpyDeviceToDevice, s));
     }
     if (P->wideSpatial) {
         if (P->visualize && cur == P->accum) {  // the debug outlines must not land in the history
-            if ((e = hipMemcpyAsync(spare, cur, Pn * 8, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+            DN_TRY(hipMemcpyAsync(spare, cur, Pn * 8, hipMemcpyDeviceToDevice, s));
             next_from(spare);
         }
-        if (!noise2 && (e = noise(2)) != hipSuccess) return e;
+        if (!noise2) DN_TRY(launch_noise(P, s, cur, 2));
         // a: a colour buffer other than the one being read; b: the other colour buffer.  With the
         // lists the first pass reads the accumulation buffer (cur) and every pass's taps outside
         // list 1 read it too (alt)
         uint2* a = cur == P->colorA ? P->colorB : cur == P->colorB ? P->colorA : spare;
         uint2* b = a == P->colorA ? P->colorB : P->colorA;
         const uint2* alt = cur;
-        // folded list chain ([tuning] dnFold): the first pass also finishes the tiles off list 1
-        // for the last (kCopy), which then runs over list 1 only with ApplyAlbedo in its store
-        const bool fold = useList && (P->listFold || (kDnSplit && P->listSplit));
-        int c0 = 0, c1 = 0;
-        tile_range(P, 1, c0, c1);
-        if (tiles(3, Q, g)) {
-            DN_MARK(2, 0);
-            if (fold) {
-                Q.cty0 = c0;
-                Q.cty1 = c1;
-                launch_s5_list<3, false, false, true>(rcp5, pk5, gList, s, Q, (const uint2*)cur, a, alt);
-            } else if (useList) {
-                launch_s5_list<3, false>(rcp5, pk5, gList, s, Q, (const uint2*)cur, a, alt);
-            } else {
-                if (rcp5) hipLaunchKernelGGL((k_spatial5<3, false, true, false>), g, b256, 0, s, Q, (const uint2*)cur, a, alt);
-                else hipLaunchKernelGGL((k_spatial5<3, false, false, false>), g, b256, 0, s, Q, (const uint2*)cur, a, alt);
-            }
-            LAUNCH_CHECK();
-            DN_MARK(2, 1);
+        const AtrousPlan plan{useList, split, fold, rcp5, pk5, gList};
+        if (tiles(P, 3, Q, g)) {
+            if (fold) tile_range(P, 1, Q.cty0, Q.cty1);
+            DN_TRY(launch_atrous<3>(P, s, plan, g, Q, cur, a, alt));
         }
-        if (tiles(2, Q, g)) {
-            DN_MARK(3, 0);
-            if (useList) {
-                launch_s5_list<6, true>(rcp5, pk5, gList, s, Q, (const uint2*)a, b, alt);
-            } else {
-                if (rcp5) hipLaunchKernelGGL((k_spatial5<6, false, true, false>), g, b256, 0, s, Q, (const uint2*)a, b, alt);
-                else hipLaunchKernelGGL((k_spatial5<6, false, false, false>), g, b256, 0, s, Q, (const uint2*)a, b, alt);
-            }
-            LAUNCH_CHECK();
-            DN_MARK(3, 1);
-        }
-        if (tiles(1, Q, g)) {
-            DN_MARK(4, 0);
-            if (fold) {
-                launch_s5_list<12, true, true>(rcp5, pk5, gList, s, Q, (const uint2*)b, a, alt);
-            } else if (useList) {
-                if (rcp5 && pk5) hipLaunchKernelGGL((k_spatial5<12, true, true, true, true>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-                else if (rcp5) hipLaunchKernelGGL((k_spatial5<12, true, true, true>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-                else if (pk5) hipLaunchKernelGGL((k_spatial5<12, true, false, true, true>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-                else hipLaunchKernelGGL((k_spatial5<12, true, false, true>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-            } else {
-                if (rcp5) hipLaunchKernelGGL((k_spatial5<12, true, true, false>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-                else hipLaunchKernelGGL((k_spatial5<12, true, false, false>), g, b256, 0, s, Q, (const uint2*)b, a, alt);
-            }
-            LAUNCH_CHECK();
-            DN_MARK(4, 1);
-        }
+        if (tiles(P, 2, Q, g)) DN_TRY(launch_atrous<6>(P, s, plan, g, Q, a, b, alt));
+        if (tiles(P, 1, Q, g)) DN_TRY(launch_atrous<12>(P, s, plan, g, Q, b, a, alt));
         cur = a;
         spare = b;
     } else {  // out of place when cur is the accumulation buffer (the next frame's history)
         uint2* dst = cur == P->accum ? spare : cur;
-        if (tiles(1, Q, g)) {
+        if (tiles(P, 1, Q, g)) {
             const size_t rows = (size_t)(Q.ty1 - Q.ty0) * 16 * W;
-            hipLaunchKernelGGL(k_apply_albedo, dim3((unsigned)((rows + 255) / 256)), b256, 0, s, Q, (const uint2*)cur, dst);
-            LAUNCH_CHECK();
+            DN_TRY(dn_launch(P, kNoMark, s, k_apply_albedo, dim3((unsigned)((rows + 255) / 256)), b256, Q, cur, dst));
         }
         cur = dst;
     }
-    P->svgfOut = cur;
-    P->histDepthDone = histDepthDone ? 1 : 0;
-    if (phase == 2) return hipSuccess;
-    return rtk_denoise_phase(P, s, 3);
+    out = cur;
+    return hipSuccess;
 }
 
-// phase 3: TemporalFilter2 onwards, up to the histogram (the tail of phase 0)
-static hipError_t denoise_phase3(DenoisePostParams* P, hipStream_t s) {
+// ---- TemporalFilter2, then PostProcessing (postprocessing.cu:5-161) up to the histogram: the
+// DownScale4 chain and the histogram over this context's rows (64-row aligned strips keep each
+// level's texels local)
+hipError_t temporal2_downscale_histogram(DenoisePostParams* P, hipStream_t s, uint2* cur, bool histDepthDone) {
     const int W = (int)P->W, H = (int)P->H;
     const size_t Pn = (size_t)W * H;
-    const dim3 b256(256);
-    const int W4 = (W + 3) / 4, H4 = (H + 3) / 4, W16b = (W4 + 3) / 4, H16b = (H4 + 3) / 4, W64 = (W16b + 3) / 4,
-              H64 = (H16b + 3) / 4;
-    hipError_t e;
-    auto tiles = [&](int halo, DenoisePostParams& Q, dim3& g) {
-        int t0, t1;
-        tile_range(P, halo, t0, t1);
-        Q = *P;
-        Q.ty0 = t0;
-        Q.ty1 = t1;
-        g = dim3((W + 15) / 16, (unsigned)(t1 > t0 ? t1 - t0 : 0));
-        return t1 > t0;
-    };
+    const Levels L(P);
     DenoisePostParams Q;
     dim3 g;
-    uint2* cur = P->svgfOut;
-    const bool histDepthDone = P->histDepthDone != 0;
     // the whole frame with every post pass on runs DownScale4 x 3 + Histogram2 + AutoExposure as
     // k_downscale_chain; TemporalFilter2 then also writes the first DownScale4 level
     const bool chain = P->postProcess && P->downScale && P->histogramOn && !P->stripLocal;
-    bool down = false;
+    const bool down = chain && P->temporal2 && P->frameNum != 1;
     if (P->temporal2) {
-        down = chain && P->frameNum != 1;
         if (P->frameNum != 1) {
-            if (tiles(1, Q, g)) {
-                DN_MARK(5, 0);
-                if (down) hipLaunchKernelGGL(k_temporal2<true>, g, b256, 0, s, Q, (const uint2*)cur, P->histColorOut);
-                else hipLaunchKernelGGL(k_temporal2<false>, g, b256, 0, s, Q, (const uint2*)cur, P->histColorOut);
-                LAUNCH_CHECK();
-                DN_MARK(5, 1);
-            }
-        } else if ((e = hipMemcpyAsync(P->histColorOut, cur, Pn * 8, hipMemcpyDeviceToDevice, s)) != hipSuccess) {
-            return e;
+            if (tiles(P, 1, Q, g))
+                DN_TRY(rtl::with_flags([&](auto dn) {
+                    return dn_launch(P, 5, s, k_temporal2<dn>, g, b256, Q, cur, P->histColorOut);
+                }, down));
+        } else {
+            DN_TRY(hipMemcpyAsync(P->histColorOut, cur, Pn * 8, hipMemcpyDeviceToDevice, s));
         }
         cur = P->histColorOut;
-        if (!histDepthDone &&
-            (e = hipMemcpyAsync(P->histDepth, P->depth, Pn * 2, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-            return e;
+        if (!histDepthDone) DN_TRY(hipMemcpyAsync(P->histDepth, P->depth, Pn * 2, hipMemcpyDeviceToDevice, s));
     }
     P->finalColor = cur;
-    if (P->hdrOut && !P->stripLocal) {  // strip-local: after the rows exchange (rtk_hdr_out, frame.cpp)
-        hipLaunchKernelGGL(k_hdr_out, dim3((unsigned)((Pn + 255) / 256)), b256, 0, s, (const uint2*)cur, P->hdrOut, Pn);
-        LAUNCH_CHECK();
-    }
-    // ---- PostProcessing (postprocessing.cu:5-161) up to the histogram: the DownScale4 chain and
-    // the histogram over this context's rows (64-row aligned strips keep each level's texels local)
+    if (P->hdrOut && !P->stripLocal)  // strip-local: after the rows exchange (rtk_hdr_out, frame.cpp)
+        DN_TRY(rtk_hdr_out(cur, P->hdrOut, Pn, s));
     if (chain) {
-        // the whole frame with every pass on: the three DownScale4 levels, Histogram2 and
-        // AutoExposure in one launch
-        DN_MARK(6, 0);
-        if (down) hipLaunchKernelGGL(k_downscale_chain<true>, dim3(W64, H64), b256, 0, s, *P, (const uint2*)cur, P->chainCounter);
-        else hipLaunchKernelGGL(k_downscale_chain<false>, dim3(W64, H64), b256, 0, s, *P, (const uint2*)cur, P->chainCounter);
-        LAUNCH_CHECK();
-        DN_MARK(6, 1);
+        DN_TRY(rtl::with_flags([&](auto fromC4) {
+            return dn_launch(P, 6, s, k_downscale_chain<fromC4>, dim3(L.W64, L.H64), b256, *P, cur, P->chainCounter);
+        }, down));
         P->exposureDone = 1;
     } else if (P->postProcess) {
         const int ra = P->stripLocal ? (int)P->rowA : 0, rb = P->stripLocal ? (int)P->rowB : H;
-        auto span = [](int a, int b, int f, int n, int& o0, int& o1) {
-            o0 = a / f;
-            o1 = (b + f - 1) / f;
+        // rows [o0, o1) of a level of n rows, f render rows each, that rows [ra, rb) cover
+        auto span = [&](int f, int n, int& o0, int& o1) {
+            o0 = ra / f;
+            o1 = (rb + f - 1) / f;
             o1 = o1 > n ? n : o1;
         };
-        if (P->downScale) {
+        // one DownScale4 level over those rows
+        auto down4 = [&](int f, const uint2* in, int Wi, int Hi, uint2* o, int Wo, int Ho) {
             int o0, o1;
-            span(ra, rb, 4, H4, o0, o1);
-            hipLaunchKernelGGL(k_downscale4, dim3((W4 * (o1 - o0) + 255) / 256), b256, 0, s, (const uint2*)cur, W, H,
-                               P->c4, W4, H4, o0, o1);
-            LAUNCH_CHECK();
-            span(ra, rb, 16, H16b, o0, o1);
-            hipLaunchKernelGGL(k_downscale4, dim3((W16b * (o1 - o0) + 255) / 256), b256, 0, s, (const uint2*)P->c4, W4,
-                               H4, P->c16, W16b, H16b, o0, o1);
-            LAUNCH_CHECK();
-            span(ra, rb, 64, H64, o0, o1);
-            hipLaunchKernelGGL(k_downscale4, dim3((W64 * (o1 - o0) + 255) / 256), b256, 0, s, (const uint2*)P->c16,
-                               W16b, H16b, P->c64, W64, H64, o0, o1);
-            LAUNCH_CHECK();
+            span(f, Ho, o0, o1);
+            return dn_launch(P, kNoMark, s, k_downscale4, dim3((Wo * (o1 - o0) + 255) / 256), b256, in, Wi, Hi, o, Wo, Ho,
+                             o0, o1);
+        };
+        if (P->downScale) {
+            DN_TRY(down4(4, cur, W, H, P->c4, L.W4, L.H4));
+            DN_TRY(down4(16, P->c4, L.W4, L.H4, P->c16, L.W16, L.H16));
+            DN_TRY(down4(64, P->c16, L.W16, L.H16, P->c64, L.W64, L.H64));
         }
         if (P->histogramOn) {
             int o0, o1;
-            span(ra, rb, 64, H64, o0, o1);
-            hipLaunchKernelGGL(k_histogram, dim3(1), dim3(1024), 0, s, (const uint2*)P->c64, W64, H64, P->histogram, o0, o1);
-            LAUNCH_CHECK();
-        } else if ((e = hipMemsetAsync(P->histogram, 0, 256, s)) != hipSuccess) {
-            return e;
+            span(64, L.H64, o0, o1);
+            DN_TRY(dn_launch(P, kNoMark, s, k_histogram, dim3(1), dim3(1024), P->c64, L.W64, L.H64, P->histogram, o0, o1));
+        } else {
+            DN_TRY(hipMemsetAsync(P->histogram, 0, 256, s));
         }
     }
     return hipSuccess;
 }
 
-extern "C" hipError_t rtk_hdr_out(const uint2* color, float4* hdr, size_t n, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_hdr_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, color, hdr, n);
-    return hipGetLastError();
+// ---- the rest of PostProcessing: AutoExposure, Bloom, LensFlare, then BicubicScale + sharpen + tone
+// map + CopyToOutput in one kernel
+hipError_t post_process(DenoisePostParams* P, hipStream_t s) {
+    const int W = (int)P->W, H = (int)P->H, Ws = (int)P->Ws, Hs = (int)P->Hs;
+    const Levels L(P);
+    uint2* cur = P->finalColor;
+    if (P->postProcess) {
+        if (!P->exposureDone)
+            DN_TRY(dn_launch(P, kNoMark, s, k_auto_exposure, dim3(1), dim3(64), P->exposure, P->histogram,
+                             (float)(L.W64 * L.H64), P->deltaTime, P->gain, P->autoExposure, P->fixedExposure));
+        // Bloom and LensFlare modify RenderColorBuffer, which here may be the next frame's
+        // history (TemporalFilter2's output): both write a colour buffer instead (full frame only).
+        uint2* post = cur == P->colorA ? P->colorB : P->colorA;
+        const dim3 g16((W + 15) / 16, (H + 15) / 16);
+        if (P->bloom) {
+            DN_TRY(dn_launch(P, kNoMark, s, k_bloom_gauss, dim3((L.W4 + 11) / 12, (L.H4 + 11) / 12), b256, P->c4, L.W4,
+                             L.H4, P->bloom4, P->exposure));
+            DN_TRY(dn_launch(P, kNoMark, s, k_bloom_gauss, dim3((L.W16 + 11) / 12, (L.H16 + 11) / 12), b256, P->c16,
+                             L.W16, L.H16, P->bloom16, P->exposure));
+            DN_TRY(dn_launch(P, kNoMark, s, k_bloom_apply, g16, b256, *P, cur, post));
+            cur = post;
+        }
+        if (P->lensFlare) {
+            DN_TRY(dn_launch(P, kNoMark, s, k_lens_flare, g16, b256, *P, cur, post));
+            cur = post;
+        }
+        P->finalColor = cur;
+    }
+    DenoisePostParams Q = *P;
+    Q.sharpen = P->postProcess && P->sharpen;
+    Q.tonemap = P->postProcess && P->tonemap;
+    int t0 = 0, t1 = (Hs + 15) / 16;
+    if (P->stripLocal) tile_range(P, 0, t0, t1);  // screen = render size for strips
+    Q.ty0 = t0;
+    Q.ty1 = t1;
+    if (t1 > t0) {
+        const dim3 gs((Ws + 15) / 16, (unsigned)(t1 - t0));
+        DN_TRY(rtl::with_flags([&](auto small) {
+            constexpr int kLds = small ? kScaleLdsSmall : kScaleLdsLarge;
+            return dn_launch(P, 7, s, k_scale_post<kLds>, gs, dim3(kScaleThreads), Q, cur);
+        }, scale_lds_small(W, Ws) && scale_lds_small(H, Hs)));
+    }
+    P->finalScaled = P->scaledB;
+    return hipSuccess;
 }
 
-extern "C" hipError_t rtk_denoise_post(DenoisePostParams* P, hipStream_t s) {
-    hipError_t e = rtk_denoise_phase(P, s, 0);
-    return e == hipSuccess ? rtk_denoise_phase(P, s, 1) : e;
+}  // namespace
+
+extern "C" hipError_t rtk_hdr_out(const uint2* color, float4* hdr, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return rtl::launch(k_hdr_out, dim3((unsigned)((n + 255) / 256)), b256, s, color, hdr, n);
+}
+
+// phase 0: TemporalSpatialDenoising + TemporalFilter2 + DownScale4 + Histogram2 (the histogram is
+// this strip's share when strip-local); phase 1: AutoExposure onwards.  A multi-GPU host sums the
+// histograms between the phases.
+extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* P, hipStream_t s, int phase) {
+    if (phase == 1) return post_process(P, s);
+    if (phase != 0) return hipErrorInvalidValue;
+    uint2* color = nullptr;
+    bool histDepthDone = false;
+    DN_TRY(temporal_spatial_denoising(P, s, color, histDepthDone));
+    return temporal2_downscale_histogram(P, s, color, histDepthDone);
 }

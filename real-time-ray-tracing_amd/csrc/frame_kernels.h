@@ -303,12 +303,10 @@ struct DenoisePostParams {
     uint32_t* chainCounter;     // k_downscale_chain's workgroup counter (zero between launches)
     int exposureDone;           // set by phase 0 when k_downscale_chain ran AutoExposure
     int histDepthInTemporal;    // k_temporal also copies depth into the history depth (per launch)
-    uint2* svgfOut;             // phase 2 -> 3: the colour buffer TemporalSpatialDenoising ended in
-    int histDepthDone;          // phase 2 -> 3: k_temporal already wrote the history depth
     uint32_t* tileList;         // active-tile lists of the noise-gated passes (denoise.hip), or null
     uint32_t tileCap;           // tiles the lists can hold (16x16 tiles of the allocated render size)
     int tileParity;             // this frame's counter set (the other one is zeroed by TemporalFilter)
-    int listUsed;               // out (phase 0 / 2): the chain ran over the lists; the host flips tileParity
+    int listUsed;               // out (phase 0): the chain ran over the lists; the host flips tileParity
     int listSplit;              // the list passes at two threads per pixel (512-thread workgroups, denoise.hip)
     int listFold;               // the last a-trous pass over list 1 only (the first finishes the other tiles)
     float rcpDepth[3];          // RN(1 / sigma_depth) of TemporalFilter, SpatialFilter7x7, the a-trous passes
@@ -320,10 +318,8 @@ struct DenoisePostParams {
 constexpr int kDnKernels = 8;  // k_temporal, k_spatial7, k_spatial5<3>, <6>, <12>, k_temporal2,
                                // k_downscale_chain, k_scale_post
 
-extern "C" hipError_t rtk_denoise_post(DenoisePostParams* p, hipStream_t stream);
-// phase 0: denoise .. DownScale4 + Histogram2; phase 1: AutoExposure .. RGBA8 (finalColor of phase 0 in).
-// Phase 0 = phase 2 (TemporalSpatialDenoising: TemporalFilter .. the a-trous passes) then phase 3
-// (TemporalFilter2 .. Histogram2).
+// phase 0: denoise .. DownScale4 + Histogram2; phase 1: AutoExposure .. RGBA8 (finalColor of phase 0 in);
+// any other phase: hipErrorInvalidValue
 extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* p, hipStream_t stream, int phase);
 // the render-size float4 HDR copy (rt_draw's hdr_out) of a denoised colour buffer
 extern "C" hipError_t rtk_hdr_out(const uint2* color, float4* hdr, size_t n, hipStream_t stream);

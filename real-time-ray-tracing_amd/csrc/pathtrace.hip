@@ -23,6 +23,7 @@
 // the other G-buffers come from sample 0.
 #include "emitter_kernels.h"
 #include "frame_kernels.h"
+#include "launch.h"
 #include "pt_common.h"
 #include "queue_trace.h"
 #include "shade.h"
@@ -1380,8 +1381,7 @@ __global__ __launch_bounds__(256) void k_fold_ray_counts(unsigned long long* dst
 
 extern "C" hipError_t rtk_fold_ray_counts(unsigned long long* dst, unsigned long long* src, hipStream_t stream) {
     static_assert(kRayCounterSlots <= 256, "one workgroup");
-    hipLaunchKernelGGL(k_fold_ray_counts, dim3(1), dim3(256), 0, stream, dst, src);
-    return hipGetLastError();
+    return rtl::launch(k_fold_ray_counts, dim3(1), dim3(256), stream, dst, src);
 }
 
 extern "C" hipError_t rtk_launch_pt_camera(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks) {
@@ -1395,12 +1395,11 @@ extern "C" hipError_t rtk_launch_pt_camera(const PathTraceParams* p, hipStream_t
     const int nSW = cam_sample_waves(p->spp);
     const int BW = nSW == 4 ? 8 : 16, BH = nSW == 1 ? 16 : 8;
     const dim3 grid((p->width + BW - 1) / BW, (p->rows + BH - 1) / BH);
-    const bool stats = p->statsOut != nullptr;
-    void (*k)(PathTraceParams) = one_round(p->spp) ? (stats ? k_pt_camera<true, true> : k_pt_camera<true, false>)
-                                                   : (stats ? k_pt_camera<false, true> : k_pt_camera<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, *p);
-    if (marks && marks[1] && (e = hipEventRecord(marks[1], stream)) != hipSuccess) return e;
-    return hipGetLastError();
+    e = rtl::with_flags(
+        [&](auto oneRound, auto stats) { return rtl::launch(k_pt_camera<oneRound, stats>, grid, dim3(256), stream, *p); },
+        one_round(p->spp), p->statsOut != nullptr);
+    if (e == hipSuccess && marks && marks[1]) e = hipEventRecord(marks[1], stream);
+    return e;
 }
 
 // hook (optional): called on the host right after each kernel is enqueued; the frame pipeline
@@ -1420,40 +1419,46 @@ dim3 shade_grid(const PathTraceParams* p, K kernel, int& cached) {
     return dim3(perCu * (p->ws.cus ? p->ws.cus : 256u));
 }
 
-template <bool kOneRound>
-void launch_shade_rounds(const PathTraceParams* p, hipStream_t stream) {
-    static int occ[6];
-    const dim3 pb(256);
-    if (p->emHeader) {  // emitter sampling: the table-reading kernel that also samples the emitter list
-        auto k = k_pt_shade0<true, true, kOneRound, true, true>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[5]), pb, 0, stream, *p);
-    } else if (p->matTable) {  // a custom material table (rt_set_materials): every class, parameters from the table
-        auto k = k_pt_shade0<true, true, kOneRound, true>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[4]), pb, 0, stream, *p);
-    } else if (p->ws.glossy && p->ws.microfacet) {  // a triangle table with both classes (rt_set_triangle_materials)
-        auto k = k_pt_shade0<true, true, kOneRound>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[3]), pb, 0, stream, *p);
-    } else if (p->ws.glossy) {
-        auto k = k_pt_shade0<true, false, kOneRound>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[0]), pb, 0, stream, *p);
-    } else if (p->ws.microfacet) {
-        auto k = k_pt_shade0<false, true, kOneRound>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[1]), pb, 0, stream, *p);
-    } else {
-        auto k = k_pt_shade0<false, false, kOneRound>;
-        hipLaunchKernelGGL(k, shade_grid(p, k, occ[2]), pb, 0, stream, *p);
-    }
+// The material variant of the shading kernels (k_pt_shade0, k_pt_resume), six in all: the table-reading
+// kernel that also samples the emitter list (emitter sampling); the table-reading kernel (a custom
+// material table, rt_set_materials: every class, parameters from the table); else the classes the
+// triangle table holds (rt_set_triangle_materials), glossy x microfacet.
+struct MatVariant {
+    bool glossy, mf, tab, nee;
+    int index() const { return nee ? 5 : tab ? 4 : 2 * glossy + mf; }
+};
+MatVariant mat_variant(const PathTraceParams* p) {
+    if (p->emHeader) return {true, true, true, true};
+    if (p->matTable) return {true, true, true, false};
+    return {p->ws.glossy != 0, p->ws.microfacet != 0, false, false};
+}
+// f(glossy, mf, tab, nee) with the variant's flags as constants
+template <class F>
+hipError_t with_material(const MatVariant& m, F&& f) {
+    return rtl::with_flags([&](auto glossy, auto mf, auto tab, auto nee) {
+        constexpr bool kTab = tab || nee;  // the table kernels have both classes compiled in
+        return f(std::bool_constant<glossy || kTab>{}, std::bool_constant<mf || kTab>{}, std::bool_constant<kTab>{}, nee);
+    }, m.glossy, m.mf, m.tab, m.nee);
 }
 
 // The shade kernel and, when the launch carries a displacement (geometry motion vectors), the motion
 // kernel right behind it: one slot for the marks and the hook, so the kernel numbers keep their meaning
-void launch_shade(const PathTraceParams* p, hipStream_t stream) {
-    if (one_round(p->spp)) launch_shade_rounds<true>(p, stream);
-    else launch_shade_rounds<false>(p, stream);
-    if (p->triDisp) {  // the list's length is known on the device only: a grid-stride loop over at most 8 workgroups per CU
+hipError_t launch_shade(const PathTraceParams* p, hipStream_t stream) {
+    static int occ[2][6];  // per round count and material variant
+    const MatVariant m = mat_variant(p);
+    const bool one = one_round(p->spp);
+    hipError_t e = with_material(m, [&](auto glossy, auto mf, auto tab, auto nee) {
+        constexpr bool kGlossy = glossy, kMF = mf, kTab = tab, kNee = nee;  // constants inside the next lambda too
+        return rtl::with_flags([&](auto oneRound) {
+            auto k = k_pt_shade0<kGlossy, kMF, oneRound, kTab, kNee>;
+            return rtl::launch(k, shade_grid(p, k, occ[one][m.index()]), dim3(256), stream, *p);
+        }, one);
+    });
+    if (e == hipSuccess && p->triDisp) {  // the list's length is known on the device only: a grid-stride loop over at most 8 workgroups per CU
         const uint32_t need = (p->rows * p->width + 255u) / 256u, cap = 8u * (p->ws.cus ? p->ws.cus : 256u);
-        hipLaunchKernelGGL(k_pt_geom_motion, dim3(need < cap ? need : cap), dim3(256), 0, stream, *p);
+        e = rtl::launch(k_pt_geom_motion, dim3(need < cap ? need : cap), dim3(256), stream, *p);
     }
+    return e;
 }
 
 hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks, const PtLaunchHook* hook,
@@ -1463,9 +1468,8 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
 extern "C" hipError_t rtk_launch_pt_shade(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks) {
     hipError_t e;
     if (marks && marks[2] && (e = hipEventRecord(marks[2], stream)) != hipSuccess) return e;
-    launch_shade(p, stream);
-    if (marks && marks[3] && (e = hipEventRecord(marks[3], stream)) != hipSuccess) return e;
-    return hipGetLastError();
+    if ((e = launch_shade(p, stream)) != hipSuccess) return e;
+    return marks && marks[3] ? hipEventRecord(marks[3], stream) : hipSuccess;
 }
 
 extern "C" hipError_t rtk_launch_pt_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t* marks,
@@ -1502,12 +1506,21 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
         return se == hipSuccess ? end() : se;
     };
     const dim3 pg(p->ws.persistBlocks), pb(256);
-    auto kernel = [&](void (*fn)(PathTraceParams), dim3 grid, hipStream_t s) {  // errors surface in hipGetLastError below
-        hipLaunchKernelGGL(fn, grid, pb, 0, s, *p);
-        return hipSuccess;
+    auto kernel = [&](void (*fn)(PathTraceParams), dim3 grid, hipStream_t s) { return rtl::launch(fn, grid, pb, s, *p); };
+    const MatVariant mat = mat_variant(p);
+    // k_pt_resume of step 3 (the material variant's) or 4 (which shades nothing; under a custom table it
+    // reads the emission of the entry a path ended on)
+    auto resume = [&](auto step) {
+        constexpr int kStep = step;
+        return with_material(mat, [&](auto glossy, auto mf, auto tab, auto nee) {
+            constexpr bool kShades = kStep == 3;
+            return kernel(k_pt_resume<kStep, kShades && mf, kShades && glossy, tab, nee>, pg, stream);
+        });
     };
+    using Step3 = std::integral_constant<int, 3>;
+    using Step4 = std::integral_constant<int, 4>;
     if (withShade) {
-        e = stage([&] { launch_shade(p, stream); return hipSuccess; });
+        e = stage([&] { return launch_shade(p, stream); });
     } else {  // enqueued by the caller on another stream: only the hook runs for kernel 1
         if (hook && hook->fn) e = hook->fn(hook->arg, k);
         ++k;
@@ -1521,7 +1534,10 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
     if (plan == PtBouncePlan::chain) {
         // kernel 2 = the fused bounce chain (trace<3> .. resume<4>); slots 3-5 stay empty, so the
         // hook's kernel numbers and the per-kernel timing slots keep their meaning
-        e = stage([&] { return kernel(p->statsOut ? k_pt_chain<true> : k_pt_chain<false>, dim3(p->ws.traceBlocks), stream); });
+        e = stage([&] {
+            return rtl::with_flags([&](auto stats) { return kernel(k_pt_chain<stats>, dim3(p->ws.traceBlocks), stream); },
+                                   p->statsOut != nullptr);
+        });
         for (int j = 3; j <= 5 && e == hipSuccess; ++j) e = stage([] { return hipSuccess; });
         if (e != hipSuccess) return e;
     } else {
@@ -1534,28 +1550,18 @@ hipError_t launch_rest(const PathTraceParams* p, hipStream_t stream, hipEvent_t*
             if (p->ws.hitRec4 == p->ws.hitRec || p->ws.hitErr4 == p->ws.hitErr) return hipErrorInvalidValue;
             if ((e = hipEventRecord(fork->traced, stream)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(fork->stream, fork->traced, 0)) != hipSuccess) return e;
-            (void)kernel(k_pt_resume3_lean, pg, fork->stream);
+            if ((e = kernel(k_pt_resume3_lean, pg, fork->stream)) != hipSuccess) return e;
             if ((e = hipEventRecord(fork->done, fork->stream)) != hipSuccess) return e;
         }
         e = stage([&] {
-            if (split) {  // the shading list first: it feeds queue 4
-                (void)kernel(p->ws.microfacet ? k_pt_resume3_shade<true> : k_pt_resume3_shade<false>, pg, stream);
-                return forked ? hipSuccess : kernel(k_pt_resume3_lean, pg, stream);
-            }
-            if (p->emHeader) return kernel(k_pt_resume<3, true, true, true, true>, pg, stream);
-            if (p->matTable) return kernel(k_pt_resume<3, true, true, true>, pg, stream);
-            return kernel(p->ws.glossy       ? (p->ws.microfacet ? k_pt_resume<3, true, true> : k_pt_resume<3, false, true>)
-                          : p->ws.microfacet ? k_pt_resume<3, true, false>
-                                             : k_pt_resume<3, false, false>, pg, stream);
+            if (!split) return resume(Step3{});
+            // the shading list first: it feeds queue 4
+            const hipError_t se = rtl::with_flags([&](auto mf) { return kernel(k_pt_resume3_shade<mf>, pg, stream); },
+                                                  p->ws.microfacet != 0);
+            return se != hipSuccess || forked ? se : kernel(k_pt_resume3_lean, pg, stream);
         });
         if (e == hipSuccess) e = stage([&] { return rtk_launch_trace_queue(p, 4, stream); });
-        // step 4 shades nothing; under a custom table it reads the emission of the entry a path ended on
-        if (e == hipSuccess)
-            e = stage([&] {
-                return kernel(p->emHeader   ? k_pt_resume<4, false, false, true, true>
-                              : p->matTable ? k_pt_resume<4, false, false, true>
-                                            : k_pt_resume<4, false, false>, pg, stream);
-            });
+        if (e == hipSuccess) e = stage([&] { return resume(Step4{}); });
         if (e == hipSuccess && forked) e = hipStreamWaitEvent(stream, fork->done, 0);  // its pathL stores
         if (e != hipSuccess) return e;
     }
