@@ -247,6 +247,53 @@ TraceCamera rt_trace_camera(const HostCamera& c) {
     return t;
 }
 
+// An LBVH set takes the current mesh's counts, and its arena the layout the build kernel's traversal
+// words assume for that batch count (traverse.h): TLAS nodes at B * 1024, triangle records behind
+// them.  The allocation is the capacity's, which holds the layout of every mesh within it.
+static void arena_place(rt_context* ctx, BvhBufs& b) {
+    b.meshSerial = ctx->meshSerial;
+    b.triCount = ctx->mesh.triCount;
+    b.triCountPadded = ctx->mesh.triCountPadded;
+    b.B = ctx->B;
+    b.tlasNodes = (char*)b.nodes + (size_t)b.B * 1024 * 64;
+    b.triPos = (float4*)((char*)b.nodes + ((size_t)b.B * 1024 + b.B) * 64);
+}
+
+// An event of the context: created where first needed, without timing unless asked for, and destroyed
+// by rt_destroy
+int rt_event(rt_context* ctx, hipEvent_t& e, bool timing) {
+    if (e) return RT_OK;
+    HIP_TRY(ctx, hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
+    ctx->events.push_back(e);
+    return RT_OK;
+}
+
+// The buffers of one LBVH set, by the capacity (rt_set_mesh), which without the config keys is the init
+// mesh: the record arena (traverse.h: BLAS nodes, TLAS nodes, triangle records, 64 B each) cleared and
+// laid out for the current mesh, the build's scratch and its zeroed launch counter.  The displacement
+// and emitter-list buffers are their features' (ensure_geometry_motion, ensure_emitter_lists).
+int alloc_bvh_set(rt_context* ctx, BvhBufs& b) {
+    if (b.counter) return RT_OK;  // allocated last: the set is complete
+    const size_t NP = ctx->capNP, B = ctx->capB;
+    RT_TRY(dalloc_once(ctx, b.nodes, arena_bytes(B, NP)));
+    RT_TRY(dalloc_once(ctx, b.triNrm, NP * 48));
+    RT_TRY(dalloc_once(ctx, b.aabbs, NP * 24));
+    RT_TRY(dalloc_once(ctx, b.batchScene, B * 24));
+    RT_TRY(dalloc_once(ctx, b.morton, B * 4096));
+    RT_TRY(dalloc_once(ctx, b.reorder, B * 4096));
+    RT_TRY(dalloc_once(ctx, b.tlasAabbs, B * 24));
+    RT_TRY(dalloc_once(ctx, b.tlasScene, 24));
+    RT_TRY(dalloc_once(ctx, b.tlasMorton, 4096));
+    RT_TRY(dalloc_once(ctx, b.tlasReorder, 4096));
+    HIP_TRY(ctx, hipMemset(b.nodes, 0, arena_bytes(B, NP)));
+    arena_place(ctx, b);
+    uint32_t* counter = nullptr;
+    RT_TRY(dalloc(ctx, &counter, 64));
+    HIP_TRY(ctx, hipMemset(counter, 0, 64));
+    b.counter = counter;
+    return RT_OK;
+}
+
 extern "C" {
 
 const char* rt_last_error(const rt_context* ctx) { return ctx ? ctx->err.c_str() : g_createError.c_str(); }
@@ -302,17 +349,6 @@ int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32
         if (adj_corners) adj_corners[slot] = (uint32_t)c;
     }
     return RT_OK;
-}
-
-// An LBVH set takes the current mesh's counts, and its arena the layout the build kernel's traversal
-// words assume for that batch count (traverse.h): TLAS nodes at B * 1024, triangle records behind
-// them.  The allocation is the capacity's, which holds the layout of every mesh within it.
-void arena_place(rt_context* ctx, BvhBufs& b) {
-    b.triCount = ctx->mesh.triCount;
-    b.triCountPadded = ctx->mesh.triCountPadded;
-    b.B = ctx->B;
-    b.tlasNodes = (char*)b.nodes + (size_t)b.B * 1024 * 64;
-    b.triPos = (float4*)((char*)b.nodes + ((size_t)b.B * 1024 + b.B) * 64);
 }
 
 int rt_create(int screen_width, int screen_height, const char* config_toml, rt_context** out) {
@@ -530,45 +566,24 @@ int rt_init(rt_context* ctx) {
     // all are CU-masked streams without priority (rt_create_stream)
     if (int rc = rt_create_stream(ctx, &ctx->ownStream, true)) return rc;
     ctx->stream = ctx->ownStream;
-    HIP_TRY(ctx, hipEventCreate(&ctx->ev0));
-    HIP_TRY(ctx, hipEventCreate(&ctx->ev1));
+    RT_TRY(rt_event(ctx, ctx->ev0, true));
+    RT_TRY(rt_event(ctx, ctx->ev1, true));
 
-    int rc;
-#define ALLOC(p, bytes) if ((rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
     // every mesh-sized buffer by the capacity (rt_set_mesh), which without the config keys is this mesh
-    const size_t capNV = ctx->capNV, capNP = ctx->capNP, capB = ctx->capB;
-    ALLOC(ctx->dVerts, capNV * 12);
-    ALLOC(ctx->dNormals, capNV * 12);
-    ALLOC(ctx->dIdx, capNP * 12);
-    // the record arena (traverse.h): BLAS nodes, TLAS nodes, triangle records, 64 B each, laid out by the
-    // batch count of the mesh a build gathers (arena_place)
-    ALLOC(ctx->dNodes, arena_bytes(capB, capNP));
-    ALLOC(ctx->dTriNrm, capNP * 48);
-    ALLOC(ctx->dAabbs, capNP * 24);
-    ALLOC(ctx->dBatchScene, capB * 24);
-    ALLOC(ctx->dMorton, capB * 4096);
-    ALLOC(ctx->dReorder, capB * 4096);
-    ALLOC(ctx->dTlasAabbs, capB * 24);
-    ALLOC(ctx->dTlasScene, 24);
-    ALLOC(ctx->dTlasMorton, 4096);
-    ALLOC(ctx->dTlasReorder, 4096);
-    ALLOC(ctx->dCounter, 64);
-    ctx->bvh[0] = BvhBufs{nullptr, ctx->dTriNrm, ctx->dAabbs, ctx->dBatchScene, ctx->dMorton, ctx->dReorder,
-                          ctx->dNodes, ctx->dTlasAabbs, ctx->dTlasScene, ctx->dTlasMorton, ctx->dTlasReorder,
-                          nullptr, ctx->dCounter};
-    arena_place(ctx, ctx->bvh[0]);
-    bvh_select(ctx, 0);
-    ALLOC(ctx->dBlueNoise, 327680);
+    const size_t capNV = ctx->capNV, capNP = ctx->capNP;
+    RT_TRY(dalloc_once(ctx, ctx->dVerts, capNV * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dNormals, capNV * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dIdx, capNP * 12));
+    RT_TRY(alloc_bvh_set(ctx, ctx->bvh[0]));
+    RT_TRY(dalloc_once(ctx, ctx->dBlueNoise, 327680));
     const size_t P = (size_t)ctx->renderW * ctx->renderH;
-    ALLOC(ctx->dHits, P * 16);
-    ALLOC(ctx->dHitNrm, P * 16);
-    ALLOC(ctx->dHitFake, P * 16);
-    ALLOC(ctx->dHitStats, P * 16);
+    RT_TRY(dalloc_once(ctx, ctx->dHits, P * 16));
+    RT_TRY(dalloc_once(ctx, ctx->dHitNrm, P * 16));
+    RT_TRY(dalloc_once(ctx, ctx->dHitFake, P * 16));
+    RT_TRY(dalloc_once(ctx, ctx->dHitStats, P * 16));
 
     HIP_TRY(ctx, hipMemcpy(ctx->dVerts, ctx->mesh.vertices.data(), (size_t)ctx->nv * 12, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->dIdx, ctx->mesh.indices.data(), (size_t)NP * 12, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemset(ctx->dCounter, 0, 64));
-    HIP_TRY(ctx, hipMemset(ctx->dNodes, 0, arena_bytes(capB, capNP)));
 
     std::string bn;
     if (!read_file(dataDir + "/bluenoise_4spp.bin", bn) || bn.size() != 327680) {
@@ -585,38 +600,36 @@ int rt_init(rt_context* ctx) {
             ctx->err = "the mesh has an index past its vertices";
             return RT_ERR_ARG;
         }
-        ALLOC(ctx->dAdjOff, (capNV + 1) * 4);
-        ALLOC(ctx->dAdjCorner, capNP * 12);
+        RT_TRY(dalloc_once(ctx, ctx->dAdjOff, (capNV + 1) * 4));
+        RT_TRY(dalloc_once(ctx, ctx->dAdjCorner, capNP * 12));
         HIP_TRY(ctx, hipMemcpy(ctx->dAdjOff, off.data(), off.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(ctx->dAdjCorner, corners.data(), corners.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, rtk_launch_smooth_normals(ctx->dVerts, ctx->dAdjOff, ctx->dAdjCorner, ctx->dIdx, ctx->nv,
                                                ctx->dNormals, ctx->stream));
     }
-#undef ALLOC
-    if ((rc = rt_frame_init(ctx)) != RT_OK) return rc;
+    RT_TRY(rt_frame_init(ctx));
     // vertex updates (rt_update_vertices*, geometry.hip): their scratch and events exist from here on,
     // so that an update only enqueues work
-    if ((rc = dalloc(ctx, &ctx->dCornerSlot, capNP * 12)) != RT_OK) return rc;
-    if ((rc = dalloc(ctx, &ctx->dContrib, capNP * 36)) != RT_OK) return rc;
+    RT_TRY(dalloc_once(ctx, ctx->dCornerSlot, capNP * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dContrib, capNP * 36));
     HIP_TRY(ctx, hipMemcpy(ctx->dCornerSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomSrc, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->geomDone, hipEventDisableTiming));
+    RT_TRY(rt_event(ctx, ctx->geomSrc));
+    RT_TRY(rt_event(ctx, ctx->geomDone));
     // device ray queries (rt_trace_rays_device): their fetch counters and events, so that a query only enqueues work
-    if ((rc = dalloc(ctx, &ctx->queryFetch, 512)) != RT_OK) return rc;
-    for (hipEvent_t* e : {&ctx->queryDone[0], &ctx->queryDone[1]})
-        HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (ctx->geomMotion && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;  // [render] geometryMotion
-    if (ctx->emitterOn && (rc = ensure_emitter_lists(ctx)) != RT_OK) return rc;    // [render] emitterSampling
+    RT_TRY(dalloc_once(ctx, ctx->queryFetch, 512));
+    for (BvhBufs& b : ctx->bvh) RT_TRY(rt_event(ctx, b.queryDone));
+    if (ctx->geomMotion) RT_TRY(ensure_geometry_motion(ctx));  // [render] geometryMotion
+    if (ctx->emitterOn) RT_TRY(ensure_emitter_lists(ctx));     // [render] emitterSampling
     // mesh sets (rt_set_mesh*, mesh.hip): the staging buffers of the host variants and the adjacency
     // sort's scratch, behind every other buffer of rt_init, so that a set only enqueues work
-    if ((rc = dalloc(ctx, &ctx->dVertStage, capNV * 12)) != RT_OK) return rc;
-    if ((rc = dalloc(ctx, &ctx->dIdxStage, capNP * 12)) != RT_OK) return rc;
+    RT_TRY(dalloc_once(ctx, ctx->dVertStage, capNV * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dIdxStage, capNP * 12));
     for (int k = 0; k < 2; ++k) {
-        if ((rc = dalloc(ctx, &ctx->dSortKeys[k], capNP * 12)) != RT_OK) return rc;
-        if ((rc = dalloc(ctx, &ctx->dSortVals[k], capNP * 12)) != RT_OK) return rc;
+        RT_TRY(dalloc_once(ctx, ctx->dSortKeys[k], capNP * 12));
+        RT_TRY(dalloc_once(ctx, ctx->dSortVals[k], capNP * 12));
     }
-    if ((rc = dalloc(ctx, &ctx->dSortTable, ((size_t)256 * kMeshTilesMax + 256) * 4)) != RT_OK) return rc;
-    if ((rc = dalloc(ctx, &ctx->dMeshBad, 64)) != RT_OK) return rc;
+    RT_TRY(dalloc_once(ctx, ctx->dSortTable, ((size_t)256 * kMeshTilesMax + 256) * 4));
+    RT_TRY(dalloc_once(ctx, ctx->dMeshBad, 64));
     HIP_TRY(ctx, hipMemset(ctx->dMeshBad, 0, 64));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->mesh.vertices = std::vector<float>();   // the device holds the mesh from here on
@@ -632,28 +645,13 @@ int rt_init(rt_context* ctx) {
 void rt_destroy(rt_context* ctx) {
     if (!ctx) return;
     if (ctx->inited) (void)sync_streams(ctx, false);  // also when the context stream is the null stream
-    for (hipEvent_t e : {ctx->overlapEv, ctx->cameraGate, ctx->specGate, ctx->specDone, ctx->buildDone[0], ctx->buildDone[1],
-                         ctx->bvhFree[0], ctx->bvhFree[1], ctx->geomSrc, ctx->geomDone, ctx->queryDone[0], ctx->queryDone[1]})
-        if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < kGbSets; ++k)
-        for (hipEvent_t e : {ctx->ptDone[k], ctx->postDone[k], ctx->camDone[k], ctx->restDone[k], ctx->gatherDone[k],
-                             ctx->leanTraced[k], ctx->leanDone[k]})
-            if (e) (void)hipEventDestroy(e);
-    for (const rt_context::MatTable& t : ctx->matPool)
-        for (hipEvent_t e : {t.read, t.specRead})
-            if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->matSrc, ctx->matDone, ctx->texSide, ctx->texLean, ctx->texDone})
-        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->events) (void)hipEventDestroy(e);
     if (ctx->sideStream) (void)hipStreamDestroy(ctx->sideStream);
     if (ctx->leanStream) (void)hipStreamDestroy(ctx->leanStream);
     if (ctx->ownPostStream) (void)hipStreamDestroy(ctx->ownPostStream);
     for (void* p : ctx->allocations) (void)hipFree(p);
     if (ctx->fr.q3Host) (void)hipHostFree(ctx->fr.q3Host);
     if (ctx->status) (void)hipHostFree(ctx->status);
-    for (hipEvent_t e : ctx->markPool)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ownStream) {
         (void)hipStreamSynchronize(ctx->ownStream);
         (void)hipStreamDestroy(ctx->ownStream);
@@ -728,52 +726,38 @@ int rt_get_info(const rt_context* ctx, rt_info* out) {
     return RT_OK;
 }
 
-void bvh_select(rt_context* ctx, int k) {
-    const BvhBufs& b = ctx->bvh[k];
-    ctx->bvhSet = k;
-    ctx->dTriPos = b.triPos;
-    ctx->dTriNrm = b.triNrm;
-    ctx->dAabbs = b.aabbs;
-    ctx->dBatchScene = b.batchScene;
-    ctx->dMorton = b.morton;
-    ctx->dReorder = b.reorder;
-    ctx->dNodes = b.nodes;
-    ctx->dTlasAabbs = b.tlasAabbs;
-    ctx->dTlasScene = b.tlasScene;
-    ctx->dTlasMorton = b.tlasMorton;
-    ctx->dTlasReorder = b.tlasReorder;
-    ctx->dTlasNodes = b.tlasNodes;
-    ctx->dCounter = b.counter;
-}
-
+// The explicit build (BuildBvhLevel1/2), which a draw issues too: into the current set on the context
+// stream, or with frame pipelining into the other set on the side stream, behind that set's last readers.
 int rt_build_bvh(rt_context* ctx) {
     if (!ctx) return RT_ERR_ARG;
     if (!ctx->inited) { ctx->err = "rt_build_bvh before rt_init"; return RT_ERR_STATE; }
     if (int rc = check_device_status(ctx)) return rc;  // a previous build's failure, once it is known
-    hipStream_t stream = ctx->stream;
+    ctx->bvhPrebuilt = false;  // an explicit build supersedes a synchronous draw's prebuild
+    if (!ctx->postStream) return build_bvh(ctx, ctx->bvhSet, ctx->stream);
+    const int k = ctx->bvhSet ^ 1;
+    if (ctx->bvh[k].readInFlight) HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->bvh[k].readDone, 0));
+    ctx->bvhSet = k;
+    return build_bvh(ctx, k, ctx->sideStream);
+}
+
+}  // extern "C"
+
+// The LBVH of the current geometry into bvh[set] on `stream`, with what follows a build on its stream:
+// the displacement records, the emitter list and, off the context stream, the set's buildDone.
+int build_bvh(rt_context* ctx, int set, hipStream_t stream) {
+    BvhBufs& b = ctx->bvh[set];
     // camera rays a synchronous draw traced ahead read this set (frame.cpp launch_spec_camera): the
     // rebuild overwrites it only after them.  It writes the same values while the geometry epoch is
     // theirs; after a vertex update it does not, and the next path trace drops them (spec_matches)
     if (ctx->fr.spec.valid) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->specDone, 0));
-    ctx->bvhPrebuilt = false;  // an explicit build supersedes a synchronous draw's prebuild
-    if (!ctx->postStream) ctx->buildOnSide[ctx->bvhSet] = false;
-    if (ctx->postStream) {  // frame pipelining: build into the other set, on the side stream
-        const int k = ctx->bvhSet ^ 1;
-        if (ctx->bvhInFlight[k]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->bvhFree[k], 0));
-        bvh_select(ctx, k);
-        stream = ctx->sideStream;
-    }
+    if (!ctx->postStream) b.buildOnSide = false;
     // the build gathers the vertices and normals of the last update, whichever stream that ran on
     if (ctx->geomDoneValid && stream != ctx->geomStream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->geomDone, 0));
-    {  // the set's first build on another mesh (rt_set_mesh): its counts and arena layout, over a cleared arena,
-       // so that what the build does not write reads zero as in a context initialised with this mesh
-        BvhBufs& b = ctx->bvh[ctx->bvhSet];
-        if (b.meshSerial != ctx->meshSerial) {
-            b.meshSerial = ctx->meshSerial;
-            arena_place(ctx, b);
-            bvh_select(ctx, ctx->bvhSet);
-            HIP_TRY(ctx, hipMemsetAsync(b.nodes, 0, arena_bytes(ctx->capB, ctx->capNP), stream));
-        }
+    // the set's first build on another mesh (rt_set_mesh): its counts and arena layout, over a cleared arena,
+    // so that what the build does not write reads zero as in a context initialised with this mesh
+    if (b.meshSerial != ctx->meshSerial) {
+        arena_place(ctx, b);
+        HIP_TRY(ctx, hipMemsetAsync(b.nodes, 0, arena_bytes(ctx->capB, ctx->capNP), stream));
     }
     BvhBuildParams p;
     p.vertices = ctx->dVerts;
@@ -782,19 +766,19 @@ int rt_build_bvh(rt_context* ctx) {
     p.triCount = ctx->mesh.triCount;
     p.triCountPadded = ctx->mesh.triCountPadded;
     p.batchCount = ctx->B;
-    p.triPos = ctx->dTriPos;
-    p.triNrm = ctx->dTriNrm;
-    p.aabbs = ctx->dAabbs;
-    p.batchSceneAabbs = ctx->dBatchScene;
-    p.morton = ctx->dMorton;
-    p.reorder = ctx->dReorder;
-    p.nodes = ctx->dNodes;
-    p.tlasAabbs = ctx->dTlasAabbs;
-    p.tlasSceneAabb = ctx->dTlasScene;
-    p.tlasMorton = ctx->dTlasMorton;
-    p.tlasReorder = ctx->dTlasReorder;
-    p.tlasNodes = ctx->dTlasNodes;
-    p.counter = ctx->dCounter;
+    p.triPos = b.triPos;
+    p.triNrm = b.triNrm;
+    p.aabbs = b.aabbs;
+    p.batchSceneAabbs = b.batchScene;
+    p.morton = b.morton;
+    p.reorder = b.reorder;
+    p.nodes = b.nodes;
+    p.tlasAabbs = b.tlasAabbs;
+    p.tlasSceneAabb = b.tlasScene;
+    p.tlasMorton = b.tlasMorton;
+    p.tlasReorder = b.tlasReorder;
+    p.tlasNodes = b.tlasNodes;
+    p.counter = b.counter;
     p.threads = (uint32_t)ctx->bvhThreads;
     p.cus = (uint32_t)ctx->cuCount;
     p.status = ctx->status;
@@ -808,66 +792,61 @@ int rt_build_bvh(rt_context* ctx) {
     // next update (which overwrites dVerts / dPrevVerts) is behind this read as it is behind the
     // gather.  The first build, a build at the previous one's epoch and a build whose predecessor's
     // positions were not kept (the feature was off) record none.
-    {
-        const int k = ctx->bvhSet;
-        ctx->dispValid[k] = false;
-        if (ctx->geomMotion && ctx->built && ctx->geomEpoch != ctx->builtEpoch && ctx->prevVertsValid &&
-            ctx->prevVertsEpoch == ctx->builtEpoch) {
-            GeomDispParams d;
-            d.vertices = ctx->dVerts;
-            d.prevVerts = ctx->dPrevVerts;
-            d.indices = ctx->dIdx;
-            d.triDisp = ctx->bvh[k].triDisp;
-            d.triCountPadded = ctx->bvh[k].triCountPadded;
-            HIP_TRY(ctx, rtk_launch_geometry_displacement(&d, stream));
-            ctx->dispValid[k] = true;
-            ctx->dispTraced[k] = false;
-        }
-        ctx->built = true;
-        ctx->builtEpoch = ctx->geomEpoch;
+    b.dispValid = false;
+    if (ctx->geomMotion && ctx->built && ctx->geomEpoch != ctx->builtEpoch && ctx->prevVertsValid &&
+        ctx->prevVertsEpoch == ctx->builtEpoch) {
+        GeomDispParams d;
+        d.vertices = ctx->dVerts;
+        d.prevVerts = ctx->dPrevVerts;
+        d.indices = ctx->dIdx;
+        d.triDisp = b.triDisp;
+        d.triCountPadded = b.triCountPadded;
+        HIP_TRY(ctx, rtk_launch_geometry_displacement(&d, stream));
+        b.dispValid = true;
+        b.dispTraced = false;
     }
+    ctx->built = true;
+    ctx->builtEpoch = ctx->geomEpoch;
     // emitter sampling: the set's emitter list from the records this build has just written, behind it on
     // its stream and ahead of buildDone, so whatever traces the set reads the list of its build.  The
     // material table is written in place behind a wait for every stream; the triangle ids may come from a
     // device set on another stream (matDone), and a later device set into the buffer read here waits for
     // listRead as it waits for the path traces that read it.
-    {
-        BvhBufs& b = ctx->bvh[ctx->bvhSet];
-        b.emBuilt = false;
-        if (emitter_active(ctx) && b.emHeader && ctx->mesh.triCount <= kEmMaxTris) {
-            const bool ids = ctx->materialOverride < 0 && ctx->dTriMat;
-            if (ids && ctx->matDevice && ctx->matDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->matDone, 0));
-            EmitterListParams e;
-            e.triPos = b.triPos;
-            e.triMat = ids ? ctx->dTriMat : nullptr;
-            e.matTable = reinterpret_cast<const float4*>(ctx->dMatTable);
-            e.materialOverride = ctx->materialOverride;
-            e.triCount = ctx->mesh.triCount;
-            e.cdfLen = emitter_cdf_len(ctx->mesh.triCount);
-            e.triWeight = b.emTriWeight;
-            e.blockCount = b.emBlockCount;
-            e.tris = b.emTris;
-            e.weights = b.emWeights;
-            e.cdf = b.emCdf;
-            e.scanSums = b.emScanSums;
-            e.header = b.emHeader;
-            HIP_TRY(ctx, rtk_launch_emitter_list(&e, stream));
-            if (ids && ctx->matPoolReady) {
-                rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
-                HIP_TRY(ctx, hipEventRecord(tab.listRead, stream));
-                tab.listValid = true;
-            }
-            b.emBuilt = true;
-            b.emCdfLen = e.cdfLen;
+    b.emBuilt = false;
+    if (emitter_active(ctx) && b.emHeader && ctx->mesh.triCount <= kEmMaxTris) {
+        const bool ids = ctx->materialOverride < 0 && ctx->dTriMat;
+        if (ids && ctx->matDevice && ctx->matDone) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->matDone, 0));
+        EmitterListParams e;
+        e.triPos = b.triPos;
+        e.triMat = ids ? ctx->dTriMat : nullptr;
+        e.matTable = reinterpret_cast<const float4*>(ctx->dMatTable);
+        e.materialOverride = ctx->materialOverride;
+        e.triCount = ctx->mesh.triCount;
+        e.cdfLen = emitter_cdf_len(ctx->mesh.triCount);
+        e.triWeight = b.emTriWeight;
+        e.blockCount = b.emBlockCount;
+        e.tris = b.emTris;
+        e.weights = b.emWeights;
+        e.cdf = b.emCdf;
+        e.scanSums = b.emScanSums;
+        e.header = b.emHeader;
+        HIP_TRY(ctx, rtk_launch_emitter_list(&e, stream));
+        if (ids && ctx->matPoolReady) {
+            rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+            HIP_TRY(ctx, hipEventRecord(tab.listRead, stream));
+            tab.listValid = true;
         }
+        b.emBuilt = true;
+        b.emCdfLen = e.cdfLen;
     }
-    if (ctx->postStream) {
-        HIP_TRY(ctx, hipEventRecord(ctx->buildDone[ctx->bvhSet], stream));
-        ctx->buildOnSide[ctx->bvhSet] = true;
-        ctx->sideBuilt[ctx->bvhSet] = true;
+    if (stream != ctx->stream) {  // the side stream: a pipelined frame's build, a synchronous draw's prebuild
+        HIP_TRY(ctx, hipEventRecord(b.buildDone, stream));
+        b.buildOnSide = b.sideBuilt = true;
     }
     return RT_OK;
 }
+
+extern "C" {
 
 // ---------------------------------------------------------------- animated geometry
 //
@@ -898,8 +877,8 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
     // the builds that still gather the old positions: a synchronous draw's prebuild on the side stream
     // (the context stream's own builds are ahead of the update there), an earlier update elsewhere
     if (u != ctx->sideStream)
-        for (int k = 0; k < 2; ++k)
-            if (ctx->sideBuilt[k]) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->buildDone[k], 0));
+        for (const BvhBufs& b : ctx->bvh)
+            if (b.sideBuilt) HIP_TRY(ctx, hipStreamWaitEvent(u, b.buildDone, 0));
     if (ctx->geomDoneValid && ctx->geomStream != u) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->geomDone, 0));
     hipEvent_t* marks = ctx->meshMarks;  // rt_time_mesh_set only
     if (mesh) {
@@ -1072,7 +1051,7 @@ int rt_set_geometry_motion(rt_context* ctx, int on) {
     if (on && (rc = ensure_geometry_motion(ctx)) != RT_OK) return rc;
     if ((on != 0) != ctx->geomMotion) {  // from the next build on: what the sets hold is dropped either way
         ctx->prevVertsValid = false;
-        ctx->dispValid[0] = ctx->dispValid[1] = false;
+        ctx->bvh[0].dispValid = ctx->bvh[1].dispValid = false;
     }
     ctx->geomMotion = on != 0;
     return RT_OK;
@@ -1246,11 +1225,9 @@ static int ensure_mat_pool(rt_context* ctx) {
     HIP_TRY(ctx, hipMemset(block, 3, missing * ctx->matBytes));
     HIP_TRY(ctx, hipMemset(block + missing * ctx->matBytes, 0, (size_t)kMatPool * 1024 + 64));
     HIP_TRY(ctx, hipStreamSynchronize(nullptr));  // this first call may block; the fills precede every stream's use
-    for (hipEvent_t* e : {&ctx->matSrc, &ctx->matDone})
-        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t* e : {&ctx->matSrc, &ctx->matDone}) RT_TRY(rt_event(ctx, *e));
     for (rt_context::MatTable& t : ctx->matPool)
-        for (hipEvent_t* e : {&t.read, &t.specRead, &t.listRead})
-            if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (hipEvent_t* e : {&t.read, &t.specRead, &t.listRead}) RT_TRY(rt_event(ctx, *e));
     uint8_t* at = block;
     for (rt_context::MatTable& t : ctx->matPool)
         if (!t.ids) {
@@ -1520,8 +1497,7 @@ int rt_reset_material_textures(rt_context* ctx) {
 
 // a context-stream user of the current LBVH waits for its build on the side stream
 int wait_bvh(rt_context* ctx) {
-    if (ctx->buildOnSide[ctx->bvhSet])
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->buildDone[ctx->bvhSet], 0));
+    if (ctx->lbvh().buildOnSide) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->lbvh().buildDone, 0));
     return RT_OK;
 }
 
@@ -1540,10 +1516,10 @@ int rt_trace_primary(rt_context* ctx, int frame_num, int with_detail) {
     p.strip = (uint32_t)ctx->stripIndex;
     p.frameNum = frame_num;
     p.bluenoise = ctx->dBlueNoise;
-    p.triPos = ctx->dTriPos;
-    p.triNrm = ctx->dTriNrm;
-    p.nodes = ctx->dNodes;
-    p.tlasNodes = ctx->dTlasNodes;
+    p.triPos = ctx->lbvh().triPos;
+    p.triNrm = ctx->lbvh().triNrm;
+    p.nodes = ctx->lbvh().nodes;
+    p.tlasNodes = ctx->lbvh().tlasNodes;
     p.hitOut = ctx->dHits;
     p.normalOut = with_detail ? ctx->dHitNrm : nullptr;
     p.fakeNormalOut = with_detail ? ctx->dHitFake : nullptr;
@@ -1704,7 +1680,7 @@ int rt_frame_marks_begin(rt_context* ctx, int frames, uint32_t kernel_mask) {
     const size_t need = (size_t)frames * 2 * kFrameKernels;
     while (ctx->markPool.size() < need) {
         hipEvent_t e = nullptr;
-        HIP_TRY(ctx, hipEventCreate(&e));
+        RT_TRY(rt_event(ctx, e, true));
         ctx->markPool.push_back(e);
     }
     ctx->markRing.assign(need, nullptr);  // unmarked kernels keep null entries (no event recorded)
@@ -1748,7 +1724,7 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
     if (!ctx) return 0;
     // the BVH arrays have the sizes of the current set's last build (before one, the init mesh's), the
     // mesh-level arrays the current mesh's (rt_set_mesh)
-    const BvhBufs& set = ctx->bvh[ctx->bvhSet];
+    const BvhBufs& set = ctx->lbvh();
     const size_t NP = set.triCountPadded, B = set.B, P = (size_t)ctx->renderW * ctx->renderH;
     if ((what & ~0xFF) != 0) {  // RT_ARR_TEX_SET(k): a colour map of texture set k
         const int base = what & 0xFF;
@@ -1826,6 +1802,8 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
     if (!ctx || !dst) return RT_ERR_ARG;
     if (!ctx->inited) { ctx->err = "rt_download before rt_init"; return RT_ERR_STATE; }
     const void* src = nullptr;
+    const BvhBufs& set = ctx->lbvh();
+    const FrameSet& qs = ctx->fr.set[ctx->fr.lastSlot];  // the bounce queues of the last path trace
     if ((what & ~0xFF) != 0) {  // RT_ARR_TEX_SET(k) | RT_ARR_TEX_ALBEDO_AO / NORMAL_ROUGHNESS
         const size_t need = rt_array_bytes(ctx, what);
         if (need == 0) { ctx->err = "unknown array, or a texture set past [scene] textureSets"; return RT_ERR_ARG; }
@@ -1841,19 +1819,19 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_NORMALS: src = ctx->dNormals; break;
         case RT_ARR_ADJ_OFFSETS: src = ctx->dAdjOff; break;
         case RT_ARR_CORNER_SLOTS: src = ctx->dCornerSlot; break;
-        case RT_ARR_TRI_POS: src = ctx->dTriPos; break;
-        case RT_ARR_TRI_NRM: src = ctx->dTriNrm; break;
-        case RT_ARR_AABBS: src = ctx->dAabbs; break;
-        case RT_ARR_MORTON: src = ctx->dMorton; break;
-        case RT_ARR_REORDER: src = ctx->dReorder; break;
-        case RT_ARR_NODES: src = ctx->dNodes; break;
-        case RT_ARR_BVH_ARENA: src = ctx->dNodes; break;
-        case RT_ARR_TLAS_AABBS: src = ctx->dTlasAabbs; break;
-        case RT_ARR_TLAS_MORTON: src = ctx->dTlasMorton; break;
-        case RT_ARR_TLAS_REORDER: src = ctx->dTlasReorder; break;
-        case RT_ARR_TLAS_NODES: src = ctx->dTlasNodes; break;
-        case RT_ARR_TLAS_SCENE_AABB: src = ctx->dTlasScene; break;
-        case RT_ARR_BATCH_SCENE_AABBS: src = ctx->dBatchScene; break;
+        case RT_ARR_TRI_POS: src = set.triPos; break;
+        case RT_ARR_TRI_NRM: src = set.triNrm; break;
+        case RT_ARR_AABBS: src = set.aabbs; break;
+        case RT_ARR_MORTON: src = set.morton; break;
+        case RT_ARR_REORDER: src = set.reorder; break;
+        case RT_ARR_NODES: src = set.nodes; break;
+        case RT_ARR_BVH_ARENA: src = set.nodes; break;
+        case RT_ARR_TLAS_AABBS: src = set.tlasAabbs; break;
+        case RT_ARR_TLAS_MORTON: src = set.tlasMorton; break;
+        case RT_ARR_TLAS_REORDER: src = set.tlasReorder; break;
+        case RT_ARR_TLAS_NODES: src = set.tlasNodes; break;
+        case RT_ARR_TLAS_SCENE_AABB: src = set.tlasScene; break;
+        case RT_ARR_BATCH_SCENE_AABBS: src = set.batchScene; break;
         case RT_ARR_HITS: src = ctx->dHits; break;
         case RT_ARR_HIT_NORMALS: src = ctx->dHitNrm; break;
         case RT_ARR_HIT_FAKE_NORMALS: src = ctx->dHitFake; break;
@@ -1876,15 +1854,15 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_TEX_ALBEDO_AO: src = ctx->fr.texAlbedo; break;
         case RT_ARR_TEX_NORMAL_ROUGHNESS: src = ctx->fr.texNormal; break;
         case RT_ARR_TEX_HEIGHT: src = ctx->fr.texHeight; break;
-        case RT_ARR_PT_QUEUE: src = ctx->fr.lastCounters ? ctx->fr.lastCounters : ctx->fr.ws.counters; break;
-        case RT_ARR_PT_Q3_ORIGINS: src = ctx->fr.camQ3[ctx->fr.lastSlot].rayO; break;
-        case RT_ARR_PT_Q3_DIRS: src = ctx->fr.camQ3[ctx->fr.lastSlot].rayD; break;
-        case RT_ARR_PT_Q4_ORIGINS: src = ctx->fr.camQ4[ctx->fr.lastSlot].rayO; break;
-        case RT_ARR_PT_Q4_DIRS: src = ctx->fr.camQ4[ctx->fr.lastSlot].rayD; break;
-        case RT_ARR_PT_Q3_BETA: src = ctx->fr.camQ3[ctx->fr.lastSlot].st1; break;
-        case RT_ARR_EMITTER_TRIS: src = ctx->bvh[ctx->bvhSet].emTris; break;
-        case RT_ARR_EMITTER_WEIGHTS: src = ctx->bvh[ctx->bvhSet].emWeights; break;
-        case RT_ARR_EMITTER_CDF: src = ctx->bvh[ctx->bvhSet].emCdf; break;
+        case RT_ARR_PT_QUEUE: src = ctx->fr.lastCounters ? ctx->fr.lastCounters : ctx->fr.set[0].counters; break;
+        case RT_ARR_PT_Q3_ORIGINS: src = qs.q3.rayO; break;
+        case RT_ARR_PT_Q3_DIRS: src = qs.q3.rayD; break;
+        case RT_ARR_PT_Q4_ORIGINS: src = qs.q4.rayO; break;
+        case RT_ARR_PT_Q4_DIRS: src = qs.q4.rayD; break;
+        case RT_ARR_PT_Q3_BETA: src = qs.q3.st1; break;
+        case RT_ARR_EMITTER_TRIS: src = set.emTris; break;
+        case RT_ARR_EMITTER_WEIGHTS: src = set.emWeights; break;
+        case RT_ARR_EMITTER_CDF: src = set.emCdf; break;
         case RT_ARR_SUN_DIR: {
             if (bytes < 16) { ctx->err = "destination too small"; return RT_ERR_ARG; }
             float* o = (float*)dst;
@@ -1920,7 +1898,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
     if (bytes < need) { ctx->err = "destination too small"; return RT_ERR_ARG; }
     if (int rc = sync_streams(ctx)) return rc;
     if (what == RT_ARR_TRI_POS) {  // the arena's 64-B triangle records -> the reference's [N][3] float4
-        HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, ctx->bvh[ctx->bvhSet].triCountPadded, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, set.triCountPadded, hipMemcpyDeviceToHost));
         return RT_OK;
     }
     if (need == 0) return RT_OK;  // an empty emitter list, or none

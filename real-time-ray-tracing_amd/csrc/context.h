@@ -57,6 +57,20 @@ struct BvhBufs {
     float* emScanSums = nullptr;
     bool emBuilt = false;       // the set's last build wrote a list; the path traces on it sample emitters
     uint32_t emCdfLen = 0;      // ... whose CDF has this length (emitter_cdf_len of that build's triCount)
+    // the set's last build on the side stream (ensure_bvh_pair creates the events)
+    hipEvent_t buildDone = nullptr;
+    bool buildOnSide = false;   // the current users of the set wait for buildDone (wait_bvh)
+    bool sideBuilt = false;     // buildDone has been recorded: a vertex update waits for it
+    // pipelined frames: the end of the last path trace or ray query that read the set, which the next
+    // build into it waits for
+    hipEvent_t readDone = nullptr;
+    bool readInFlight = false;
+    bool dispValid = false;     // the set's build recorded a displacement (triDisp)
+    bool dispTraced = false;    // ... and a path trace has applied it: later ones on that build do not
+    // device ray queries on a context without a post stream: the end of the last query that read the set,
+    // which a synchronous draw's prebuild into it waits for (a pipelined context records readDone instead)
+    hipEvent_t queryDone = nullptr;
+    bool queryInFlight = false;
 };
 
 // G-buffer sets in flight with frame pipelining: with four, frame f+4's camera rays wait for the
@@ -71,6 +85,36 @@ constexpr int kGbSets = RTX_GB_SETS;  // G-buffer / camera-output sets in flight
 // on the device for the readers of the buffer it writes; with 4, a host that sets once per frame
 // writes the buffer last read three frames back, whose path trace ended long before.
 constexpr int kMatPool = 4;
+
+// What exists once per G-buffer / camera-output set (FrameResources::set).  Set 0 is allocated by
+// rt_frame_init, the others on demand (alloc_frame_set); the events by the call that first needs them.
+struct FrameSet {
+    uint2* color = nullptr;     // the G-buffers; any of them may be the caller's (rt_bind_buffer)
+    uint2* normal = nullptr;
+    uint2* albedo = nullptr;
+    uint16_t* depth = nullptr;
+    uint32_t* motion = nullptr;
+    // camera-kernel outputs (the camera rays of frame f+1 are traced while the shade / trace kernels
+    // of frame f still read their set's hit records) and the counter block (PtWorkspace::counters)
+    float4* hit0Rec = nullptr;
+    float* hit0Err = nullptr;
+    uint32_t* surface = nullptr;
+    uint32_t* counters = nullptr;
+    // the bounce queues with their hit records: a set's own when the shade kernel runs on the side
+    // stream (shadeOnSide: frame f+1's shade appends to its queues while frame f's tracers and resume
+    // kernels still read theirs) or ahead of a synchronous draw; a set without them uses set 0's
+    PtQueue q3{}, q4{};
+    float4* hitRec = nullptr;
+    float* hitErr = nullptr;
+    float4* pathL = nullptr;
+    uint32_t* pending = nullptr;
+    uint32_t* shade3 = nullptr;  // queue 3's shading list (PtWorkspace::shade3; [tuning] resumeSplit)
+    bool inFlight = false;       // a denoise on the post stream reads the G-buffers (until postDone)
+    bool camInFlight = false;    // the rest of a pipelined path trace reads the camera outputs (until restDone)
+    hipEvent_t ptDone = nullptr, postDone = nullptr, camDone = nullptr, restDone = nullptr;
+    hipEvent_t gatherDone = nullptr;  // the caller's G-buffer gathers (rt_set_gather_stream)
+    hipEvent_t leanTraced = nullptr, leanDone = nullptr;  // fork and join of the split resume<3>'s lean pass
+};
 
 struct FrameResources {
     bool ready = false;
@@ -96,34 +140,22 @@ struct FrameResources {
     uint2* texAlbedo = nullptr;
     uint2* texNormal = nullptr;
     uint16_t* texHeight = nullptr;  // SoilHeight (ushort chain; feeds only the reference's disabled displacement)
-    // path-trace G-buffer (pathtrace.cuh:11-128): the set the last path trace wrote.  With a
-    // post stream (rt_set_post_stream) the path tracer cycles through kGbSets sets, so the
+    // path-trace G-buffer (pathtrace.cuh:11-128): set[gbSet] is the set the last path trace wrote.
+    // With a post stream (rt_set_post_stream) the path tracer cycles through kGbSets sets, so the
     // camera rays of frame f+1 and the rest of frame f are traced while frame f-1 is denoised;
-    // without one it always uses set 0.
-    uint2* gColor[kGbSets] = {};
-    uint2* gNormal[kGbSets] = {};
-    uint2* gAlbedo[kGbSets] = {};
-    uint16_t* gDepth[kGbSets] = {};
-    uint32_t* gMotion[kGbSets] = {};
+    // synchronous draws alternate two (spec_on), and otherwise the set stays.
+    FrameSet set[kGbSets];
     int gbSet = 0;
-    bool setInFlight[kGbSets] = {};  // a denoise on the post stream reads this set
-    uint2* color = nullptr;
-    uint2* normal = nullptr;
-    uint2* albedo = nullptr;
-    uint16_t* depth = nullptr;
-    uint32_t* motion = nullptr;
+    FrameSet& cur() { return set[gbSet]; }
+    const FrameSet& cur() const { return set[gbSet]; }
     uint32_t* rays = nullptr;
     uint4* ptStats = nullptr;
     unsigned long long* rayCounter = nullptr;
-    PtWorkspace ws{};              // wavefront queues of the path tracer (pathtrace.hip)
-    // camera-kernel outputs, one slot per G-buffer set (the camera rays of frame f+1 are traced
-    // while the shade/trace kernels of frame f still read slot f's hit records)
-    float4* camHit0Rec[kGbSets] = {};
-    float* camHit0Err[kGbSets] = {};
-    uint32_t* camSurface[kGbSets] = {};
-    uint32_t* camCount[kGbSets] = {};  // counter block per slot (PtWorkspace::counters)
+    // the non-buffer fields of every launch's workspace (cap, cus, block counts, chain); the buffers
+    // are a FrameSet's (frame.cpp bind_workspace)
+    PtWorkspace ws{};
     uint32_t* lastCounters = nullptr;  // the block of the last path trace (RT_ARR_PT_QUEUE)
-    // serial frames: three counter blocks in turn, syncCount[0] = camCount[0]; the resolve of a
+    // serial frames: three counter blocks in turn, syncCount[0] = set[0].counters; the resolve of a
     // frame using block b zeroes block b + 2 (syncZeroed), so the camera kernel of the frame after
     // next needs no memset — and the next frame's, traced ahead (spec), has a zeroed block of its own
     uint32_t* syncCount[3] = {};
@@ -144,16 +176,6 @@ struct FrameResources {
     bool gbBound = false;            // a G-buffer is the caller's (rt_bind_buffer): no set rotation
     unsigned long long* specRayCounter = nullptr;  // the rays of the launches ahead (folded in when used)
     int specCounts = 0;  // specRayCounter holds: 0 nothing, 1 the counts of used launches (to fold), 2 dropped ones
-    bool camInFlight[kGbSets] = {};
-    // ... and the bounce queues with their hit records, one slot per set when the shade kernel
-    // runs on the side stream (shadeOnSide: frame f+1's shade appends to its queues while frame
-    // f's tracers and resume kernels still read theirs); slot 0 is `ws`'s own buffers
-    PtQueue camQ3[kGbSets] = {}, camQ4[kGbSets] = {};
-    float4* camHitRec[kGbSets] = {};
-    float* camHitErr[kGbSets] = {};
-    float4* camPathL[kGbSets] = {};
-    uint32_t* camPending[kGbSets] = {};
-    uint32_t* camShade3[kGbSets] = {};  // queue 3's shading list (PtWorkspace::shade3; [tuning] resumeSplit)
     int lastSlot = 0;                  // slot of the last path trace (RT_ARR_PT_Q*)
     // queue 3's length after the last serial path trace, copied to pinned host memory behind it
     // (the fused chain's on/off choice for serial frames)
@@ -165,7 +187,7 @@ struct FrameResources {
     HistCamera hist{};
     bool histValid = false;
     // denoise + post (denoising.cu, postprocessing.cu)
-    uint2* colorB = nullptr;       // ping-pong partner of color
+    uint2* colorB = nullptr;       // ping-pong partner of the set's color
     uint2* accum = nullptr;        // AccumulationColorBuffer (the latest)
     uint2* accumAlt = nullptr;     // the list chain writes this one and swaps (null: in place only)
     bool accumBound = false;       // accum is the caller's (rt_bind_buffer): the list chain copies back
@@ -291,19 +313,17 @@ struct rt_context {
     hipStream_t ownPostStream = nullptr;  // created by an asynchronous rt_draw_device (destroyed by rt_destroy)
     hipStream_t sideStream = nullptr;  // pipelining: LBVH build + camera rays of the next frame
     hipStream_t leanStream = nullptr;  // pipelining: the forked lean pass of the split resume<3> (resumeSplit 2)
-    hipEvent_t leanTraced[kGbSets] = {}, leanDone[kGbSets] = {};  // its fork and join, per set as restDone
-    hipEvent_t ptDone[kGbSets] = {}, postDone[kGbSets] = {}, overlapEv = nullptr;
+    hipEvent_t overlapEv = nullptr;
     rt_collective_fn hook = nullptr;     // multi-GPU strip-local denoise exchanges (rt_set_collective_hook)
     void* hookArg = nullptr;
     uint32_t hookStages = (1u << RT_HOOK_HISTOGRAM) | (1u << RT_HOOK_ROWS);  // rt_set_hook_stages
     hipStream_t gatherStream = nullptr;  // optional: the caller's G-buffer gathers (rt_set_gather_stream)
     bool gatherOn = false;               // gatherStream is set (it may be the null stream)
-    hipEvent_t gatherDone[kGbSets] = {};
-    bool postGather = false;             // the pending denoise also waits for gatherDone[its set]
-    hipEvent_t buildDone[2] = {}, bvhFree[2] = {}, camDone[kGbSets] = {}, restDone[kGbSets] = {};
-    bool bvhInFlight[2] = {false, false}, buildOnSide[2] = {false, false};
+    bool postGather = false;             // the pending denoise also waits for its set's gatherDone
     BvhBufs bvh[2];
-    int bvhSet = 0;
+    int bvhSet = 0;                      // the set the next path trace, ray query and download read
+    BvhBufs& lbvh() { return bvh[bvhSet]; }
+    const BvhBufs& lbvh() const { return bvh[bvhSet]; }
     bool bvhPrebuilt = false;  // synchronous draws: the next frame's LBVH is being built into set bvhSet ^ 1
     uint64_t prebuiltEpoch = 0;  // ... from the geometry of this epoch; a draw at another epoch rebuilds
     // animated geometry (rt_update_vertices*).  The build's gather and the normals
@@ -314,7 +334,6 @@ struct rt_context {
     hipEvent_t geomDone = nullptr;      // the last update's end
     hipStream_t geomStream = nullptr;   // ... and the stream it ran on
     bool geomDoneValid = false;         // geomDone is recorded and a stream may still have to wait for it
-    bool sideBuilt[2] = {false, false}; // buildDone[k] has been recorded (a build of set k on the side stream)
     uint32_t* dCornerSlot = nullptr;    // corner -> slot in the vertex -> corner CSR (dAdjCorner's inverse)
     float* dContrib = nullptr;          // the corners' normal contributions in CSR order (geometry.hip)
     float* dVertStage = nullptr;        // rt_update_vertices' / rt_set_mesh's host positions, rt_time_stage(5, 6)'s copy
@@ -335,8 +354,6 @@ struct rt_context {
     uint64_t prevVertsEpoch = 0;
     bool built = false;                 // an LBVH has been built, at geometry epoch builtEpoch (the last build's)
     uint64_t builtEpoch = 0;
-    bool dispValid[2] = {false, false};   // set k's build recorded a displacement (bvh[k].triDisp)
-    bool dispTraced[2] = {false, false};  // ... and a path trace has applied it: later ones on that build do not
     // per-triangle materials (rt_set_triangle_materials): null until the first set and after a reset,
     // and then every launch is the one of a context without the feature.  The pool below keeps the
     // allocation across resets; the host copy gives the census of ids (triMatCount) and from it the
@@ -395,12 +412,8 @@ struct rt_context {
     hipEvent_t texSide = nullptr, texLean = nullptr, texDone = nullptr;
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
-    // and the setters that change the stream drain it), and on a context without a post stream the
-    // end of the last query that read LBVH set k, which a synchronous draw's prebuild into that set
-    // waits for (a pipelined context records bvhFree[k] instead, as its path traces do)
+    // and the setters that change the stream drain it)
     uint32_t* queryFetch = nullptr;
-    hipEvent_t queryDone[2] = {};
-    bool queryInFlight[2] = {false, false};
     // frame pipelining: rt_denoise_post(f) is enqueued on the post stream only once the next
     // path trace has enqueued kernel `overlapAfter` (so it fills the trace stages' idle tails), or
     // at the next host read / denoise call, whichever comes first
@@ -430,19 +443,6 @@ struct rt_context {
     uint32_t* dIdx = nullptr;
     uint32_t* dAdjOff = nullptr;
     uint32_t* dAdjCorner = nullptr;
-    float4* dTriPos = nullptr;
-    float4* dTriNrm = nullptr;
-    float* dAabbs = nullptr;
-    float* dBatchScene = nullptr;
-    uint32_t* dMorton = nullptr;
-    uint32_t* dReorder = nullptr;
-    void* dNodes = nullptr;
-    float* dTlasAabbs = nullptr;
-    float* dTlasScene = nullptr;
-    uint32_t* dTlasMorton = nullptr;
-    uint32_t* dTlasReorder = nullptr;
-    void* dTlasNodes = nullptr;
-    uint32_t* dCounter = nullptr;
     uint8_t* dBlueNoise = nullptr;
     float4* dHits = nullptr;
     float4* dHitNrm = nullptr;
@@ -451,6 +451,7 @@ struct rt_context {
     FrameResources fr{};  // path-trace / denoise / post buffers (frame_kernels.h)
 
     std::vector<void*> allocations;
+    std::vector<hipEvent_t> events;  // every event the context created (rt_event), destroyed by rt_destroy
     // device arena (rt_dalloc_bytes): buffers up to kArenaMaxBuffer are carved from 256-MiB chunks
     char* arenaPtr = nullptr;
     size_t arenaUsed = 0, arenaCap = 0;
@@ -466,6 +467,11 @@ struct rt_context {
         }                                                                             \
     } while (0)
 
+#define RT_TRY(expr)                         \
+    do {                                     \
+        if (int rc__ = (expr)) return rc__;  \
+    } while (0)
+
 int rt_dalloc_bytes(rt_context* ctx, void** p, size_t bytes);  // hipMalloc, freed by rt_destroy
 template <typename T>
 int dalloc(rt_context* ctx, T** p, size_t bytes) {
@@ -474,6 +480,11 @@ int dalloc(rt_context* ctx, T** p, size_t bytes) {
     *p = (T*)q;
     return rc;
 }
+template <typename T>
+int dalloc_once(rt_context* ctx, T*& p, size_t bytes) {  // a buffer allocated on first use, kept from then on
+    return p ? RT_OK : dalloc(ctx, &p, bytes);
+}
+int rt_event(rt_context* ctx, hipEvent_t& e, bool timing = false);  // context.cpp: created if null, destroyed by rt_destroy
 int rt_create_stream(rt_context* ctx, hipStream_t* s, bool high);  // context.cpp: renderer streams
 extern "C" int ensure_bvh_pair(rt_context* ctx);  // frame.cpp: second LBVH set, side stream, build events
 int rt_frame_init(rt_context* ctx);  // frame.cpp: sky tables, textures, G-buffers
@@ -483,8 +494,8 @@ int check_device_status(rt_context* ctx);  // frame.cpp: kernel failure reports 
 bool strip_local_denoise(const rt_context* ctx, uint32_t& a, uint32_t& b);  // frame.cpp: next denoise's rows
 extern "C" int copy_rgba_out(rt_context* ctx, void* dst);  // frame.cpp: the last frame's RGBA8 to host memory
 extern "C" size_t rt_alloc_bytes(const rt_context* ctx, int name);  // frame.cpp: allocated size of a render buffer
-extern "C" void bvh_select(rt_context* ctx, int k);  // context.cpp: point the dTriPos.. views at bvh[k]
-extern "C" void arena_place(rt_context* ctx, BvhBufs& b);  // context.cpp: set b takes the current mesh's counts and arena layout
+int alloc_bvh_set(rt_context* ctx, BvhBufs& b);  // context.cpp: an LBVH set's buffers, arena cleared and placed
+int build_bvh(rt_context* ctx, int set, hipStream_t stream);  // context.cpp: the LBVH of the current geometry into bvh[set]
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
 extern "C" int ensure_emitter_lists(rt_context* ctx);  // context.cpp: the existing LBVH sets' emitter-list buffers
 inline bool emitter_active(const rt_context* ctx) { return ctx->emitterOn && ctx->matCustom && ctx->matEmits; }

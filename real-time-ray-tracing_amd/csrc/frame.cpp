@@ -191,15 +191,12 @@ HistCamera hist_of(const HostCamera& c) {
 
 }  // namespace
 
-// point the G-buffer views at set fr.gbSet
-void select_gbuffers(FrameResources& fr) {
-    const int k = fr.gbSet;
-    if (fr.renderColor == fr.color) fr.renderColor = fr.gColor[k];
-    fr.color = fr.gColor[k];
-    fr.normal = fr.gNormal[k];
-    fr.albedo = fr.gAlbedo[k];
-    fr.depth = fr.gDepth[k];
-    fr.motion = fr.gMotion[k];
+// The next path trace goes into set k; RenderColorBuffer (rt_get_buffer) follows when it is the old
+// set's colour buffer, and stays when it is a denoise output.
+static void use_frame_set(FrameResources& fr, int k) {
+    const uint2* old = fr.cur().color;
+    fr.gbSet = k;
+    if (fr.renderColor == old) fr.renderColor = fr.cur().color;
 }
 
 // the denoise/post chain of one frame on stream s: phase 0, the histogram exchange, phase 1, the
@@ -280,11 +277,11 @@ int run_denoise(rt_context* ctx, DenoisePostParams& p, hipStream_t s) {
 int issue_pending_post(rt_context* ctx) {
     if (!ctx->postPending) return RT_OK;
     ctx->postPending = false;
-    const int set = ctx->postPendingSet;
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->postStream, ctx->ptDone[set], 0));
-    if (ctx->postGather) HIP_TRY(ctx, hipStreamWaitEvent(ctx->postStream, ctx->gatherDone[set], 0));
+    const FrameSet& set = ctx->fr.set[ctx->postPendingSet];
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->postStream, set.ptDone, 0));
+    if (ctx->postGather) HIP_TRY(ctx, hipStreamWaitEvent(ctx->postStream, set.gatherDone, 0));
     if (int rc = run_denoise(ctx, ctx->postParams, ctx->postStream)) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->postDone[set], ctx->postStream));
+    HIP_TRY(ctx, hipEventRecord(set.postDone, ctx->postStream));
     ctx->fr.renderColor = ctx->postParams.finalColor;  // the launcher's buffer plan names them
     ctx->fr.scaledColor = ctx->postParams.finalScaled;
     return RT_OK;
@@ -441,6 +438,38 @@ void update_dynamic_resolution(rt_context* ctx, float dt) {
 static int upload_texture_chain(rt_context* ctx, uint32_t set, int which, const uint16_t* texels, int width, int height,
                                 int channels);
 
+// G-buffer / camera-output set k, every buffer at the allocation (largest) size: the G-buffers, the
+// camera outputs with the counter block and, with `queues`, the bounce queues with their hit records
+// (a set without them uses set 0's).  What exists stays, so a later call may add the queues.
+static int alloc_frame_set(rt_context* ctx, int k, bool queues) {
+    FrameSet& s = ctx->fr.set[k];
+    const size_t P = (size_t)ctx->allocW * ctx->allocH, strip = (size_t)ctx->allocW * ctx->allocStripRows;
+    const size_t cap = ctx->fr.ws.cap;
+    RT_TRY(dalloc_once(ctx, s.color, P * 8));
+    RT_TRY(dalloc_once(ctx, s.normal, P * 8));
+    RT_TRY(dalloc_once(ctx, s.albedo, P * 8));
+    RT_TRY(dalloc_once(ctx, s.depth, P * 2));
+    RT_TRY(dalloc_once(ctx, s.motion, P * 4));
+    RT_TRY(dalloc_once(ctx, s.hit0Rec, cap * 16));
+    RT_TRY(dalloc_once(ctx, s.hit0Err, cap * 4));
+    RT_TRY(dalloc_once(ctx, s.surface, strip * 4));
+    RT_TRY(dalloc_once(ctx, s.counters, kWsCounterWords * 4));
+    if (!queues) return RT_OK;
+    for (PtQueue* q : {&s.q3, &s.q4}) {
+        RT_TRY(dalloc_once(ctx, q->rayO, cap * 16));
+        RT_TRY(dalloc_once(ctx, q->rayD, cap * 16));
+        RT_TRY(dalloc_once(ctx, q->st0, cap * 16));
+        RT_TRY(dalloc_once(ctx, q->st1, cap * 16));
+        RT_TRY(dalloc_once(ctx, q->st2, cap * 16));
+    }
+    RT_TRY(dalloc_once(ctx, s.hitRec, cap * 16));
+    RT_TRY(dalloc_once(ctx, s.hitErr, cap * 4));
+    RT_TRY(dalloc_once(ctx, s.pathL, cap * 16));
+    RT_TRY(dalloc_once(ctx, s.pending, strip * 4));
+    if (ctx->tune.resumeSplit > 0) RT_TRY(dalloc_once(ctx, s.shade3, cap * 4));
+    return RT_OK;
+}
+
 int rt_frame_init(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
     std::string err;
@@ -449,75 +478,37 @@ int rt_frame_init(rt_context* ctx) {
         if (!load_sky_tables(rt_data_dir() + "/sky_tables.bin", t, err)) { ctx->err = err; return RT_ERR_IO; }
         g_tables = std::move(t);
     }
-    int rc;
-#define ALLOC(p, bytes) if ((rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    ALLOC(fr.solar, 1800 * 4);
-    ALLOC(fr.limb, 60 * 4);
-    ALLOC(fr.cie, 30 * 4);
-    ALLOC(fr.sky, (size_t)kSkySize * 16);
-    ALLOC(fr.skyPdf, (size_t)kSkySize * 4);
-    ALLOC(fr.skyCdf, (size_t)kSkySize * 4);
-    ALLOC(fr.sun, (size_t)kSunSize * 16);
-    ALLOC(fr.sunPdf, (size_t)kSunSize * 4);
-    ALLOC(fr.sunCdf, (size_t)kSunSize * 4);
-    ALLOC(fr.scanSums, 512 * 4);
-    ALLOC(fr.skyTree, (size_t)kSkyTreeNodes * 4);
-    ALLOC(fr.sunTree, (size_t)kSunTreeNodes * 4);
-    ALLOC(fr.lightSel, 16);
+    RT_TRY(dalloc_once(ctx, fr.solar, 1800 * 4));
+    RT_TRY(dalloc_once(ctx, fr.limb, 60 * 4));
+    RT_TRY(dalloc_once(ctx, fr.cie, 30 * 4));
+    RT_TRY(dalloc_once(ctx, fr.sky, (size_t)kSkySize * 16));
+    RT_TRY(dalloc_once(ctx, fr.skyPdf, (size_t)kSkySize * 4));
+    RT_TRY(dalloc_once(ctx, fr.skyCdf, (size_t)kSkySize * 4));
+    RT_TRY(dalloc_once(ctx, fr.sun, (size_t)kSunSize * 16));
+    RT_TRY(dalloc_once(ctx, fr.sunPdf, (size_t)kSunSize * 4));
+    RT_TRY(dalloc_once(ctx, fr.sunCdf, (size_t)kSunSize * 4));
+    RT_TRY(dalloc_once(ctx, fr.scanSums, 512 * 4));
+    RT_TRY(dalloc_once(ctx, fr.skyTree, (size_t)kSkyTreeNodes * 4));
+    RT_TRY(dalloc_once(ctx, fr.sunTree, (size_t)kSunTreeNodes * 4));
+    RT_TRY(dalloc_once(ctx, fr.lightSel, 16));
     // texture sets ([scene] textureSets): the sets of one map are one allocation, set k k * kTexTexels in
-    ALLOC(fr.texAlbedo, (size_t)ctx->texSets * kTexTexels * 8);
-    ALLOC(fr.texNormal, (size_t)ctx->texSets * kTexTexels * 8);
-    ALLOC(fr.texHeight, (size_t)kTexTexels * 2);
+    RT_TRY(dalloc_once(ctx, fr.texAlbedo, (size_t)ctx->texSets * kTexTexels * 8));
+    RT_TRY(dalloc_once(ctx, fr.texNormal, (size_t)ctx->texSets * kTexTexels * 8));
+    RT_TRY(dalloc_once(ctx, fr.texHeight, (size_t)kTexTexels * 2));
     HIP_TRY(ctx, hipMemset(fr.texHeight, 0, (size_t)kTexTexels * 2));
     const size_t P = (size_t)ctx->renderW * ctx->renderH;
-    ALLOC(fr.color, P * 8);
-    ALLOC(fr.normal, P * 8);
-    ALLOC(fr.albedo, P * 8);
-    ALLOC(fr.depth, P * 2);
-    ALLOC(fr.motion, P * 4);
-    fr.gColor[0] = fr.color;
-    fr.gNormal[0] = fr.normal;
-    fr.gAlbedo[0] = fr.albedo;
-    fr.gDepth[0] = fr.depth;
-    fr.gMotion[0] = fr.motion;
-    ALLOC(fr.rays, P * 4);
-    ALLOC(fr.ptStats, P * 16);
-    ALLOC(fr.rayCounter, (size_t)kRayCounterSlots * kRayCounterStride * 8);
+    RT_TRY(dalloc_once(ctx, fr.rays, P * 4));
+    RT_TRY(dalloc_once(ctx, fr.ptStats, P * 16));
+    RT_TRY(dalloc_once(ctx, fr.rayCounter, (size_t)kRayCounterSlots * kRayCounterStride * 8));
     {  // wavefront workspace: one entry per traced sample of the strip
         const size_t cap = (size_t)ctx->renderW * ctx->stripRows * ctx->spp;
         if (cap >= (1ull << 31)) { ctx->err = "strip x spp too large for the path-trace queues"; return RT_ERR_ARG; }
         PtWorkspace& ws = fr.ws;
         ws.cap = (uint32_t)cap;
-        ALLOC(ws.hit0Rec, cap * 16);
-        ALLOC(ws.hit0Err, cap * 4);
-        for (PtQueue* q : {&ws.q3, &ws.q4}) {
-            ALLOC(q->rayO, cap * 16);
-            ALLOC(q->rayD, cap * 16);
-            ALLOC(q->st0, cap * 16);
-            ALLOC(q->st1, cap * 16);
-            ALLOC(q->st2, cap * 16);
-        }
-        ALLOC(ws.hitRec, cap * 16);
-        ALLOC(ws.hitErr, cap * 4);
-        ALLOC(ws.pathL, cap * 16);
-        if (ctx->tune.resumeSplit > 0) ALLOC(fr.camShade3[0], cap * 4);
-        ALLOC(ws.pending, (size_t)ctx->renderW * ctx->stripRows * 4);
-        ALLOC(ws.surface, (size_t)ctx->renderW * ctx->stripRows * 4);
-        ALLOC(fr.camCount[0], kWsCounterWords * 4);
-        ALLOC(fr.syncCount[1], kWsCounterWords * 4);
-        ALLOC(fr.syncCount[2], kWsCounterWords * 4);
-        fr.syncCount[0] = fr.camCount[0];
-        fr.camQ3[0] = ws.q3;
-        fr.camQ4[0] = ws.q4;
-        fr.camHitRec[0] = ws.hitRec;
-        fr.camHitErr[0] = ws.hitErr;
-        fr.camPathL[0] = ws.pathL;
-        fr.camPending[0] = ws.pending;
-        fr.camHit0Rec[0] = ws.hit0Rec;
-        fr.camHit0Err[0] = ws.hit0Err;
-        fr.camSurface[0] = ws.surface;
-        ws.counters = fr.camCount[0];
-        ws.fetch = ws.counters + 64;
+        RT_TRY(alloc_frame_set(ctx, 0, true));  // set 0 has its queues from the start
+        RT_TRY(dalloc_once(ctx, fr.syncCount[1], kWsCounterWords * 4));
+        RT_TRY(dalloc_once(ctx, fr.syncCount[2], kWsCounterWords * 4));
+        fr.syncCount[0] = fr.set[0].counters;
         int dev = 0, cus = 0;
         HIP_TRY(ctx, hipGetDevice(&dev));
         HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -544,39 +535,38 @@ int rt_frame_init(rt_context* ctx) {
         ws.chain = (uint32_t)tn.chain;  // [tuning] chain = "off" | "serial" | "always" (default serial)
         ws.trace4Blocks = (uint32_t)(cus * trace4PerCu);
     }
-    ALLOC(fr.colorB, P * 8);
-    ALLOC(fr.accum, P * 8);
-    ALLOC(fr.accumAlt, P * 8);  // the list chain's other accumulation buffer (denoise.hip active-tile lists)
-    ALLOC(fr.histBuf[0], P * 8);
-    ALLOC(fr.histBuf[1], P * 8);
-    ALLOC(fr.histDepth, P * 2);
+    RT_TRY(dalloc_once(ctx, fr.colorB, P * 8));
+    RT_TRY(dalloc_once(ctx, fr.accum, P * 8));
+    RT_TRY(dalloc_once(ctx, fr.accumAlt, P * 8));  // the list chain's other accumulation buffer (denoise.hip active-tile lists)
+    RT_TRY(dalloc_once(ctx, fr.histBuf[0], P * 8));
+    RT_TRY(dalloc_once(ctx, fr.histBuf[1], P * 8));
+    RT_TRY(dalloc_once(ctx, fr.histDepth, P * 2));
     const size_t W = (size_t)ctx->renderW, H = (size_t)ctx->renderH;
     const size_t W4 = (W + 3) / 4, H4 = (H + 3) / 4, W16 = (W4 + 3) / 4, H16 = (H4 + 3) / 4;
-    ALLOC(fr.noise8, ((W + 7) / 8) * ((H + 7) / 8) * 2);
-    ALLOC(fr.noise16, ((W + 15) / 16) * ((H + 15) / 16) * 2);
-    ALLOC(fr.chainCounter, 4);
+    RT_TRY(dalloc_once(ctx, fr.noise8, ((W + 7) / 8) * ((H + 7) / 8) * 2));
+    RT_TRY(dalloc_once(ctx, fr.noise16, ((W + 15) / 16) * ((H + 15) / 16) * 2));
+    RT_TRY(dalloc_once(ctx, fr.chainCounter, 4));
     HIP_TRY(ctx, hipMemset(fr.chainCounter, 0, 4));
     {  // active-tile lists (denoise.hip): 2 x 2 x 16 counters 128 B apart, then 2 x 16 partitions of entries
         fr.tileCap = (uint32_t)(((W + 15) / 16) * ((H + 15) / 16));
         const size_t words = 2 * 2 * 16 * 32 + 2 * 16 * (size_t)(fr.tileCap / 16 + 1);
-        ALLOC(fr.tileList, words * 4);
+        RT_TRY(dalloc_once(ctx, fr.tileList, words * 4));
         HIP_TRY(ctx, hipMemset(fr.tileList, 0, words * 4));
     }
-    ALLOC(fr.c4, W4 * H4 * 8);
-    ALLOC(fr.c16, W16 * H16 * 8);
-    ALLOC(fr.c64, ((W16 + 3) / 4) * ((H16 + 3) / 4) * 8);
-    ALLOC(fr.bloom4, W4 * H4 * 8);
-    ALLOC(fr.bloom16, W16 * H16 * 8);
-    ALLOC(fr.histogram, 256);
-    ALLOC(fr.exposure, 16);
+    RT_TRY(dalloc_once(ctx, fr.c4, W4 * H4 * 8));
+    RT_TRY(dalloc_once(ctx, fr.c16, W16 * H16 * 8));
+    RT_TRY(dalloc_once(ctx, fr.c64, ((W16 + 3) / 4) * ((H16 + 3) / 4) * 8));
+    RT_TRY(dalloc_once(ctx, fr.bloom4, W4 * H4 * 8));
+    RT_TRY(dalloc_once(ctx, fr.bloom16, W16 * H16 * 8));
+    RT_TRY(dalloc_once(ctx, fr.histogram, 256));
+    RT_TRY(dalloc_once(ctx, fr.exposure, 16));
     const size_t Ps = (size_t)ctx->screenW * ctx->screenH;
-    ALLOC(fr.scaledA, Ps * 8);
-    ALLOC(fr.scaledB, Ps * 8);
-    ALLOC(fr.rgba, Ps * 4);
+    RT_TRY(dalloc_once(ctx, fr.scaledA, Ps * 8));
+    RT_TRY(dalloc_once(ctx, fr.scaledB, Ps * 8));
+    RT_TRY(dalloc_once(ctx, fr.rgba, Ps * 4));
     fr.outRgba = fr.rgba;
     fr.outPitch = (uint32_t)ctx->screenW;
-    ALLOC(fr.hdr, P * 16);
-#undef ALLOC
+    RT_TRY(dalloc_once(ctx, fr.hdr, P * 16));
     HIP_TRY(ctx, hipMemcpy(fr.solar, g_tables.solar.data(), 1800 * 4, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(fr.limb, g_tables.limb.data(), 60 * 4, hipMemcpyHostToDevice));
     std::vector<float> cie(30);
@@ -599,11 +589,11 @@ int rt_frame_init(rt_context* ctx) {
             for (uint2* map : {fr.texAlbedo, fr.texNormal})
                 HIP_TRY(ctx, hipMemcpy(map + (size_t)k * kTexTexels, map, (size_t)kTexTexels * 8, hipMemcpyDeviceToDevice));
     }
-    HIP_TRY(ctx, hipMemset(fr.color, 0, P * 8));
-    HIP_TRY(ctx, hipMemset(fr.normal, 0, P * 8));
-    HIP_TRY(ctx, hipMemset(fr.albedo, 0, P * 8));
-    HIP_TRY(ctx, hipMemset(fr.depth, 0, P * 2));
-    HIP_TRY(ctx, hipMemset(fr.motion, 0, P * 4));
+    HIP_TRY(ctx, hipMemset(fr.set[0].color, 0, P * 8));
+    HIP_TRY(ctx, hipMemset(fr.set[0].normal, 0, P * 8));
+    HIP_TRY(ctx, hipMemset(fr.set[0].albedo, 0, P * 8));
+    HIP_TRY(ctx, hipMemset(fr.set[0].depth, 0, P * 2));
+    HIP_TRY(ctx, hipMemset(fr.set[0].motion, 0, P * 4));
     HIP_TRY(ctx, hipMemset(fr.rays, 0, P * 4));
     HIP_TRY(ctx, hipMemset(fr.ptStats, 0, P * 16));
     HIP_TRY(ctx, hipMemset(fr.rayCounter, 0, (size_t)kRayCounterSlots * kRayCounterStride * 8));
@@ -615,7 +605,7 @@ int rt_frame_init(rt_context* ctx) {
     HIP_TRY(ctx, hipMemset(fr.histogram, 0, 256));
     const float exposure0[4] = {1.0f, 1.0f, 1.0f, 1.0f};  // init.cu:331-333
     HIP_TRY(ctx, hipMemcpy(fr.exposure, exposure0, 16, hipMemcpyHostToDevice));
-    fr.renderColor = fr.color;
+    fr.renderColor = fr.set[0].color;
     fr.scaledColor = fr.scaledB;
     fr.ready = true;
     return RT_OK;
@@ -672,8 +662,7 @@ int rt_upload_texture_set_device(rt_context* ctx, const rt_texture_upload* u) {
                    " ([scene] textureSets)";
         return RT_ERR_ARG;
     }
-    for (hipEvent_t* e : {&ctx->texSide, &ctx->texLean, &ctx->texDone})
-        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t* e : {&ctx->texSide, &ctx->texLean, &ctx->texDone}) RT_TRY(rt_event(ctx, *e));
     hipStream_t s = ctx->stream;
     if (u->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)u->ready_event, 0));
     if (ctx->sideStream) {
@@ -726,43 +715,34 @@ static int upload_texture_chain(rt_context* ctx, uint32_t set, int which, const 
 extern "C" {
 
 namespace {
-// workspace slot k (1 .. kGbSets - 1): the camera outputs, and with `queues` the bounce queues with
-// their hit records (slot 0 is fr.ws's own buffers); allocated once, full size
-int alloc_ws_slot(rt_context* ctx, int k, bool queues) {
-    FrameResources& fr = ctx->fr;
-    int rc = RT_OK;
-#define ALLOC(p, bytes) if (!(p) && (rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    const size_t cap = fr.ws.cap, strip = (size_t)ctx->allocW * ctx->allocStripRows;
-    ALLOC(fr.camHit0Rec[k], cap * 16);
-    ALLOC(fr.camHit0Err[k], cap * 4);
-    ALLOC(fr.camSurface[k], strip * 4);
-    ALLOC(fr.camCount[k], kWsCounterWords * 4);
-    if (queues) {
-        for (PtQueue* q : {&fr.camQ3[k], &fr.camQ4[k]}) {
-            ALLOC(q->rayO, cap * 16);
-            ALLOC(q->rayD, cap * 16);
-            ALLOC(q->st0, cap * 16);
-            ALLOC(q->st1, cap * 16);
-            ALLOC(q->st2, cap * 16);
-        }
-        ALLOC(fr.camHitRec[k], cap * 16);
-        ALLOC(fr.camHitErr[k], cap * 4);
-        ALLOC(fr.camPathL[k], cap * 16);
-        ALLOC(fr.camPending[k], strip * 4);
-        if (ctx->tune.resumeSplit > 0) ALLOC(fr.camShade3[k], cap * 4);
-    }
-#undef ALLOC
-    return rc;
+// the bounce-queue slot of a path trace into set g: the set's own queues when allocated (shadeOnSide,
+// a synchronous draw's launches ahead), else set 0's
+int queue_slot(const FrameResources& fr, int g) { return fr.set[g].q3.rayO ? g : 0; }
+
+// the buffers of a launch's workspace: the camera outputs and counter block of `cam`, the bounce queues of `q`
+void bind_workspace(PtWorkspace& ws, const FrameSet& cam, const FrameSet& q) {
+    ws.hit0Rec = cam.hit0Rec;
+    ws.hit0Err = cam.hit0Err;
+    ws.surface = cam.surface;
+    ws.counters = cam.counters;
+    ws.fetch = ws.counters + 64;
+    ws.q3 = q.q3;
+    ws.q4 = q.q4;
+    ws.hitRec = q.hitRec;
+    ws.hitErr = q.hitErr;
+    ws.pathL = q.pathL;
+    ws.pending = q.pending;
 }
 
-// The launch parameters of frame `frame_num`'s path trace into G-buffer / camera-output set g, with
-// that set's counter block (the serial frames' block, the stream plan and the bookkeeping are
-// rt_path_trace's).  Zero-filled first, so that two calls with the same state compare equal byte
-// for byte (the synchronous draws' camera rays traced ahead, launch_spec_camera).  Returns the
-// bounce-queue slot.
-int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const HostCamera& hc, int g,
-                   PathTraceParams& p) {
+// The launch parameters of frame `frame_num`'s path trace into the G-buffers and camera outputs of set
+// `cam`, with that set's counter block and the bounce queues of set `q` (the serial frames' block, the
+// stream plan and the bookkeeping are rt_path_trace's).  Zero-filled first, so that two calls with the
+// same state compare equal byte for byte (the synchronous draws' camera rays traced ahead,
+// launch_spec_camera).
+void fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const HostCamera& hc, const FrameSet& cam,
+                    const FrameSet& q, PathTraceParams& p) {
     const FrameResources& fr = ctx->fr;
+    const BvhBufs& bvh = ctx->lbvh();  // the build the frame is traced on (rt_set_mesh: its triangle count)
     memset(&p, 0, sizeof p);
     p.cam = rt_trace_camera(hc);
     p.tanHalfFov[0] = hc.tanHalfFov[0];
@@ -782,15 +762,15 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.spp = (uint32_t)ctx->spp;
     p.invSpp = (ctx->spp & (ctx->spp - 1)) == 0 ? 1.0f / (float)ctx->spp : 0.0f;  // exact for a power of two
     p.materialOverride = ctx->materialOverride;
-    p.triCount = ctx->bvh[ctx->bvhSet].triCount;  // of the build the frame is traced on (rt_set_mesh)
+    p.triCount = bvh.triCount;
     p.bluenoise = ctx->dBlueNoise;
-    p.triPos = ctx->dTriPos;
-    p.triNrm = ctx->dTriNrm;
+    p.triPos = bvh.triPos;
+    p.triNrm = bvh.triNrm;
     // geometry motion vectors: the displacement this LBVH set's build recorded, for the first path
     // trace on it (rt_path_trace marks it traced); null: the launch sequence has no motion kernel
-    p.triDisp = ctx->dispValid[ctx->bvhSet] && !ctx->dispTraced[ctx->bvhSet] ? ctx->bvh[ctx->bvhSet].triDisp : nullptr;
-    p.nodes = ctx->dNodes;
-    p.tlasNodes = ctx->dTlasNodes;
+    p.triDisp = bvh.dispValid && !bvh.dispTraced ? bvh.triDisp : nullptr;
+    p.nodes = bvh.nodes;
+    p.tlasNodes = bvh.tlasNodes;
     p.texAlbedo = fr.texAlbedo;
     p.texNormal = fr.texNormal;
     p.skyBuffer = fr.sky;
@@ -804,30 +784,19 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
     p.cosThetaMax = fr.cosThetaMax;
     p.oneMinusCosThetaMax = 1.0f - fr.cosThetaMax;
     sun_frame(fr.sunDir, p.sunT, p.sunB);
-    p.colorOut = fr.gColor[g];
-    p.normalOut = fr.gNormal[g];
-    p.albedoOut = fr.gAlbedo[g];
-    p.depthOut = fr.gDepth[g];
-    p.motionOut = fr.gMotion[g];
+    p.colorOut = cam.color;
+    p.normalOut = cam.normal;
+    p.albedoOut = cam.albedo;
+    p.depthOut = cam.depth;
+    p.motionOut = cam.motion;
     p.raysOut = with_detail ? fr.rays : nullptr;
     p.statsOut = with_detail ? fr.ptStats : nullptr;
     p.rayCounter = fr.rayCounter;
     p.ws = fr.ws;
-    p.ws.hit0Rec = fr.camHit0Rec[g];
-    p.ws.hit0Err = fr.camHit0Err[g];
-    p.ws.surface = fr.camSurface[g];
-    p.ws.counters = fr.camCount[g];
-    p.ws.fetch = p.ws.counters + 64;
-    const int qs = fr.camQ3[g].rayO ? g : 0;  // bounce-queue slot: per set when allocated (shadeOnSide)
-    p.ws.q3 = fr.camQ3[qs];
-    p.ws.q4 = fr.camQ4[qs];
-    p.ws.hitRec = fr.camHitRec[qs];
-    p.ws.hitErr = fr.camHitErr[qs];
-    p.ws.pathL = fr.camPathL[qs];
-    p.ws.pending = fr.camPending[qs];
+    bind_workspace(p.ws, cam, q);
     p.ws.hitRec4 = p.ws.hitRec;  // one stream: queue 3's records are dead once queue 4 is traced
     p.ws.hitErr4 = p.ws.hitErr;
-    p.ws.shade3 = fr.camShade3[qs];  // null: resume<3> unsplit ([tuning] resumeSplit = 0)
+    p.ws.shade3 = q.shade3;  // null: resume<3> unsplit ([tuning] resumeSplit = 0)
     {  // material table (init.cu:215-251): only mirror / glass ids make steps 1-2 trace, only id 4 is
        // MICROFACET (rt_material_classes is the rule).  The override wins over the triangle table,
        // which such a launch does not get; without either it is the reference table, 3 / 6: no class
@@ -849,15 +818,13 @@ int fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const 
         if (p.matTable) p.ws.glossy = p.ws.microfacet = 1;
         p.ws.closest4 = ctx->matCustom && ctx->matEmits ? 1 : 0;
         // emitter sampling: the list of the build this launch traces, when that build wrote one
-        const BvhBufs& set = ctx->bvh[ctx->bvhSet];
-        if (emitter_active(ctx) && set.emBuilt && p.matTable) {
-            p.emHeader = set.emHeader;
-            p.emTris = set.emTris;
-            p.emCdf = set.emCdf;
+        if (emitter_active(ctx) && bvh.emBuilt && p.matTable) {
+            p.emHeader = bvh.emHeader;
+            p.emTris = bvh.emTris;
+            p.emCdf = bvh.emCdf;
             p.emitterQ = ctx->emitterQ;
         }
     }
-    return qs;
 }
 
 // Synchronous draws trace the next frame's camera rays ahead (launch_spec_camera): one GPU, no
@@ -911,21 +878,20 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     if (!ctx->inited) { ctx->err = "rt_path_trace before rt_init"; return RT_ERR_STATE; }
     FrameResources& fr = ctx->fr;
     if (ctx->postStream) {  // frame pipelining: trace into the set no denoise still reads
-        fr.gbSet = (fr.gbSet + 1) % kGbSets;
-        select_gbuffers(fr);
-        if (fr.setInFlight[fr.gbSet]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->postDone[fr.gbSet], 0));
+        use_frame_set(fr, (fr.gbSet + 1) % kGbSets);
+        if (fr.cur().inFlight) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, fr.cur().postDone, 0));
     } else if (spec_on(ctx)) {  // synchronous frames alternate two sets: the next one's camera rays go ahead
-        fr.gbSet ^= 1;
-        select_gbuffers(fr);
+        use_frame_set(fr, fr.gbSet ^ 1);
     }
     int rc = update_sky(ctx);
     if (rc != RT_OK) return rc;
     HostCamera hc;
     rt_camera_update(ctx->camera, ctx->renderW, ctx->renderH, hc);
     if (frame_num == 1 || !fr.histValid) fr.hist = hist_of(hc);  // kernel.cu:133-136
-    const int g = fr.gbSet;  // camera-output slot = G-buffer set
+    const int g = fr.gbSet, qs = queue_slot(fr, g);  // camera-output slot = G-buffer set
+    FrameSet& set = fr.set[g];
     PathTraceParams p;
-    const int qs = fill_pt_params(ctx, frame_num, with_detail, hc, g, p);
+    fill_pt_params(ctx, frame_num, with_detail, hc, set, fr.set[qs], p);
     if (!ctx->postStream) {  // serial frames: the counter block the resolve before last zeroed
         const int b = fr.syncIdx;
         p.ws.counters = fr.syncCount[b];
@@ -967,8 +933,8 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     hipStream_t cs = side ? ctx->sideStream : ctx->stream;
     p.ws.shadeClaim = !ctx->postStream;  // dynamic batch claims in synchronous frames (pathtrace.hip)
     if (side) {
-        if (fr.setInFlight[g]) HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->postDone[g], 0));
-        if (fr.camInFlight[g]) HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->restDone[g], 0));
+        if (set.inFlight) HIP_TRY(ctx, hipStreamWaitEvent(cs, set.postDone, 0));
+        if (set.camInFlight) HIP_TRY(ctx, hipStreamWaitEvent(cs, set.restDone, 0));
         if (ctx->cameraGated) HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->cameraGate, 0));
     } else if ((rc = wait_bvh(ctx)) != RT_OK) {
         return rc;
@@ -1004,15 +970,15 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         HIP_TRY(ctx, rtk_launch_pt_camera(&p, cs, ctx->ptMarks));
     }
     // the shade kernel follows on the side stream, so it runs beside the previous frame's queue
-    // tracers instead of after them (its bounce queues are this set's own, camQ3[g] ..)
+    // tracers instead of after them (its bounce queues are this set's own)
     const bool shadeSide = side && ctx->shadeOnSide && qs == g;
     if (shadeSide) HIP_TRY(ctx, rtk_launch_pt_shade(&p, cs, ctx->ptMarks));
     if (side) {
-        HIP_TRY(ctx, hipEventRecord(ctx->camDone[g], cs));
+        HIP_TRY(ctx, hipEventRecord(set.camDone, cs));
         // overlapAfter 0: the previous frame's denoise waits only for that frame's path trace
         // (everything on the context stream so far), not for this frame's camera rays and shade
         if (ctx->overlapAfter == 0 && ctx->postPending) HIP_TRY(ctx, issue_overlapped_post(ctx));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->camDone[g], 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, set.camDone, 0));
     }
     PtLaunchHook hook{overlap_hook, ctx};
     const bool askQ3 = !side && !fr.q3Pending;  // serial frames: queue 3's length for the next chain choice
@@ -1028,8 +994,8 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     // The lean pass of the split resume<3> on its own stream (resumeSplit 2): pipelined one-GPU frames
     // only; serial frames, detail launches and strip ranks keep one stream.  Queue 4's hit records then
     // go to this set's camera-hit planes, which nothing reads once the shade kernel is done (the set's
-    // next camera kernel waits for restDone[g]).
-    PtLeanFork lean{ctx->leanStream, ctx->leanTraced[g], ctx->leanDone[g]};
+    // next camera kernel waits for its restDone).
+    PtLeanFork lean{ctx->leanStream, set.leanTraced, set.leanDone};
     const bool fork = side && plan == PtBouncePlan::split && ctx->leanStream && ctx->stripCount == 1;
     if (fork) {
         p.ws.hitRec4 = p.ws.hit0Rec;
@@ -1052,7 +1018,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         HIP_TRY(ctx, hipEventRecord(tab.read, ctx->stream));
         tab.readValid = true;
     }
-    if (p.triDisp) ctx->dispTraced[ctx->bvhSet] = true;  // later path traces on this build see no motion of the geometry
+    if (p.triDisp) ctx->lbvh().dispTraced = true;  // later path traces on this build see no motion of the geometry
     if (!ctx->postStream) {  // block b + 2 is zeroed by this frame's resolve, enqueued above
         const int b = fr.syncIdx;
         fr.syncZeroed[(b + 2) % 3] = true;
@@ -1060,12 +1026,12 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     }
     if (ctx->postPending && (rc = issue_pending_post(ctx)) != RT_OK) return rc;
     if (ctx->postStream) {
-        HIP_TRY(ctx, hipEventRecord(ctx->restDone[g], ctx->stream));
-        fr.camInFlight[g] = true;
-        HIP_TRY(ctx, hipEventRecord(ctx->bvhFree[ctx->bvhSet], ctx->stream));
-        ctx->bvhInFlight[ctx->bvhSet] = true;
+        HIP_TRY(ctx, hipEventRecord(set.restDone, ctx->stream));
+        set.camInFlight = true;
+        HIP_TRY(ctx, hipEventRecord(ctx->lbvh().readDone, ctx->stream));
+        ctx->lbvh().readInFlight = true;
     }
-    fr.renderColor = fr.color;
+    fr.renderColor = set.color;
     fr.hist = hist_of(hc);  // HistoryCamera::Setup after PathTrace (kernel.cu:357)
     fr.histValid = true;
     ctx->lastFrame = frame_num;
@@ -1132,12 +1098,13 @@ int rt_denoise_post(rt_context* ctx, int frame_num, int with_hdr) {
             if (rt_div_rcp_ok(sig[k])) p.rcpDepthOk |= 1 << k;
         }
     }
-    p.colorA = fr.color;
+    FrameSet& set = fr.cur();  // the set the frame's path trace wrote
+    p.colorA = set.color;
     p.colorB = fr.colorB;
-    p.normal = fr.normal;
-    p.albedo = fr.albedo;
-    p.depth = fr.depth;
-    p.motion = fr.motion;
+    p.normal = set.normal;
+    p.albedo = set.albedo;
+    p.depth = set.depth;
+    p.motion = set.motion;
     p.accum = fr.accum;
     p.histColor = fr.histBuf[fr.histIdx];
     p.histColorOut = fr.histBuf[fr.histIdx ^ 1];
@@ -1225,17 +1192,17 @@ int rt_denoise_post(rt_context* ctx, int frame_num, int with_hdr) {
         // frame's path trace and any G-buffer gathers)
         int rc = issue_pending_post(ctx);
         if (rc != RT_OK) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ptDone[fr.gbSet], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(set.ptDone, ctx->stream));
         ctx->postGather = ctx->gatherOn;
-        if (ctx->postGather) HIP_TRY(ctx, hipEventRecord(ctx->gatherDone[fr.gbSet], ctx->gatherStream));
+        if (ctx->postGather) HIP_TRY(ctx, hipEventRecord(set.gatherDone, ctx->gatherStream));
         ctx->postParams = p;
         ctx->postPendingSet = fr.gbSet;
         ctx->postPending = true;
-        fr.setInFlight[fr.gbSet] = true;
+        set.inFlight = true;
     } else {
         if (ctx->gatherOn) {
-            HIP_TRY(ctx, hipEventRecord(ctx->gatherDone[0], ctx->gatherStream));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->gatherDone[0], 0));
+            HIP_TRY(ctx, hipEventRecord(fr.set[0].gatherDone, ctx->gatherStream));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, fr.set[0].gatherDone, 0));
         }
         if (int rc = run_denoise(ctx, p, ctx->stream)) return rc;
         fr.renderColor = p.finalColor;
@@ -1266,27 +1233,15 @@ namespace {
 // by the previous frame, which has finished, or by a device ray query enqueued since
 // (rt_trace_rays_device), which may not have: the side stream waits for the last such query.
 int prebuild_next_bvh(rt_context* ctx) {
-    int rc;
-    if ((rc = ensure_bvh_pair(ctx)) != RT_OK) return rc;
-    const int cur = ctx->bvhSet;
-    if (ctx->queryInFlight[cur ^ 1]) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->queryDone[cur ^ 1], 0));
-        ctx->queryInFlight[cur ^ 1] = false;
+    RT_TRY(ensure_bvh_pair(ctx));
+    const int next = ctx->bvhSet ^ 1;
+    BvhBufs& b = ctx->bvh[next];
+    if (b.queryInFlight) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, b.queryDone, 0));
+        b.queryInFlight = false;
     }
-    bvh_select(ctx, cur ^ 1);
-    hipStream_t keep = ctx->stream;  // no post stream: rt_build_bvh builds on ctx->stream
-    ctx->stream = ctx->sideStream;
-    rc = rt_build_bvh(ctx);
-    ctx->stream = keep;
-    if (rc == RT_OK) {
-        if (hipEventRecord(ctx->buildDone[cur ^ 1], ctx->sideStream) != hipSuccess) {
-            ctx->err = "hipEventRecord (LBVH prebuild)";
-            rc = RT_ERR_HIP;
-        }
-        ctx->buildOnSide[cur ^ 1] = true;
-        ctx->sideBuilt[cur ^ 1] = true;
-    }
-    bvh_select(ctx, cur);
+    int rc = check_device_status(ctx);  // a previous build's failure, as in rt_build_bvh
+    if (rc == RT_OK) rc = build_bvh(ctx, next, ctx->sideStream);
     ctx->bvhPrebuilt = rc == RT_OK;
     ctx->prebuiltEpoch = ctx->geomEpoch;
     ctx->prebuiltMatSerial = ctx->matSerial;
@@ -1297,22 +1252,13 @@ int prebuild_next_bvh(rt_context* ctx) {
 // ahead (allocated at full size, once)
 int ensure_sync_spec(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
-    int rc;
-    const size_t P = (size_t)ctx->allocW * ctx->allocH;
-#define ALLOC(p, bytes) if (!(p) && (rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    ALLOC(fr.gColor[1], P * 8);
-    ALLOC(fr.gNormal[1], P * 8);
-    ALLOC(fr.gAlbedo[1], P * 8);
-    ALLOC(fr.gDepth[1], P * 2);
-    ALLOC(fr.gMotion[1], P * 4);
-#undef ALLOC
-    if ((rc = alloc_ws_slot(ctx, 1, true)) != RT_OK) return rc;  // with bounce queues: the shade goes ahead too
+    RT_TRY(alloc_frame_set(ctx, 1, true));  // with bounce queues: the shade goes ahead too
     if (!fr.specRayCounter) {  // zero between uses (rtk_fold_ray_counts)
-        if ((rc = dalloc(ctx, &fr.specRayCounter, (size_t)kRayCounterSlots * kRayCounterStride * 8)) != RT_OK) return rc;
+        RT_TRY(dalloc_once(ctx, fr.specRayCounter, (size_t)kRayCounterSlots * kRayCounterStride * 8));
         HIP_TRY(ctx, hipMemset(fr.specRayCounter, 0, (size_t)kRayCounterSlots * kRayCounterStride * 8));
     }
-    for (hipEvent_t* e : {&ctx->specGate, &ctx->specDone})
-        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    RT_TRY(rt_event(ctx, ctx->specGate));
+    RT_TRY(rt_event(ctx, ctx->specDone));
     fr.specReady = true;
     return RT_OK;
 }
@@ -1334,7 +1280,8 @@ int launch_spec_camera(rt_context* ctx) {
     HostCamera hc;
     rt_camera_update(ctx->camera, ctx->renderW, ctx->renderH, hc);
     PathTraceParams p;  // on this frame's LBVH set (spec_matches)
-    fill_pt_params(ctx, ctx->nextFrame, 0, hc, fr.gbSet ^ 1, p);
+    const int g = fr.gbSet ^ 1;
+    fill_pt_params(ctx, ctx->nextFrame, 0, hc, fr.set[g], fr.set[queue_slot(fr, g)], p);
     const int b = fr.syncIdx;
     p.ws.counters = fr.syncCount[b];
     p.ws.countersZeroed = fr.syncZeroed[b] ? 1 : 0;
@@ -1388,7 +1335,7 @@ int enqueue_frame(rt_context* ctx, uint32_t* target, uint32_t pitch, bool hdr) {
     if (ctx->bvhPrebuilt && !ctx->postStream && ctx->prebuiltEpoch == ctx->geomEpoch &&
         (!emitter_active(ctx) || ctx->prebuiltMatSerial == ctx->matSerial)) {
         ctx->bvhPrebuilt = false;
-        bvh_select(ctx, ctx->bvhSet ^ 1);  // the path trace waits for its build (wait_bvh)
+        ctx->bvhSet ^= 1;  // the path trace waits for its build (wait_bvh)
     } else if ((rc = rt_build_bvh(ctx)) != RT_OK) {
         return rc;
     }
@@ -1478,8 +1425,7 @@ int rt_set_gather_stream(rt_context* ctx, void* stream) {
     if (!ctx->inited) { ctx->err = "rt_set_gather_stream before rt_init"; return RT_ERR_STATE; }
     int rc = sync_streams(ctx, false);
     if (rc != RT_OK) return rc;
-    for (int k = 0; k < kGbSets; ++k)
-        if (!ctx->gatherDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->gatherDone[k], hipEventDisableTiming));
+    for (FrameSet& s : ctx->fr.set) RT_TRY(rt_event(ctx, s.gatherDone));
     ctx->gatherOn = stream != RT_STREAM_OFF;  // NULL is the null stream, as in rt_set_stream
     ctx->gatherStream = ctx->gatherOn ? (hipStream_t)stream : nullptr;
     return RT_OK;
@@ -1488,38 +1434,13 @@ int rt_set_gather_stream(rt_context* ctx, void* stream) {
 // The second LBVH set, the side stream and the build events: frame f+1's build beside frame f
 // (pipelined frames, and the prebuild of synchronous draws)
 int ensure_bvh_pair(rt_context* ctx) {
-    int rc;
-#define ALLOC(p, bytes) if (!(p) && (rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    {
-        const size_t NP = ctx->capNP, B = ctx->capB;  // by the capacity, as in rt_init
-        BvhBufs& b = ctx->bvh[1];
-        if (!b.nodes) {  // the record arena (traverse.h), as in rt_init
-            ALLOC(b.nodes, arena_bytes(B, NP));
-            HIP_TRY(ctx, hipMemset(b.nodes, 0, arena_bytes(B, NP)));
-            arena_place(ctx, b);
-            b.meshSerial = ctx->meshSerial;
-        }
-        ALLOC(b.triNrm, NP * 48);
-        if (ctx->geomMotion) ALLOC(b.triDisp, NP * 48);  // else with rt_set_geometry_motion (ensure_geometry_motion)
-        ALLOC(b.aabbs, NP * 24);
-        ALLOC(b.batchScene, B * 24);
-        ALLOC(b.morton, B * 4096);
-        ALLOC(b.reorder, B * 4096);
-        ALLOC(b.tlasAabbs, B * 24);
-        ALLOC(b.tlasScene, 24);
-        ALLOC(b.tlasMorton, 4096);
-        ALLOC(b.tlasReorder, 4096);
-        if (!b.counter) {
-            ALLOC(b.counter, 64);
-            HIP_TRY(ctx, hipMemset(b.counter, 0, 64));
-        }
-    }
-#undef ALLOC
-    if (ctx->emitterOn && (rc = ensure_emitter_lists(ctx)) != RT_OK) return rc;  // else with rt_set_emitter_sampling
+    RT_TRY(alloc_bvh_set(ctx, ctx->bvh[1]));
+    if (ctx->geomMotion) RT_TRY(ensure_geometry_motion(ctx));  // else with rt_set_geometry_motion
+    if (ctx->emitterOn) RT_TRY(ensure_emitter_lists(ctx));     // else with rt_set_emitter_sampling
     // lowest priority: it should fill what the trace chain leaves idle
-    if (!ctx->sideStream && (rc = rt_create_stream(ctx, &ctx->sideStream, false)) != RT_OK) return rc;
-    for (hipEvent_t* e : {&ctx->buildDone[0], &ctx->buildDone[1], &ctx->bvhFree[0], &ctx->bvhFree[1]})
-        if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (!ctx->sideStream) RT_TRY(rt_create_stream(ctx, &ctx->sideStream, false));
+    for (BvhBufs& b : ctx->bvh) RT_TRY(rt_event(ctx, b.buildDone));
+    for (BvhBufs& b : ctx->bvh) RT_TRY(rt_event(ctx, b.readDone));
     return RT_OK;
 }
 
@@ -1529,49 +1450,32 @@ int rt_set_post_stream(rt_context* ctx, void* stream) {
     int rc = sync_streams(ctx, false);
     if (rc != RT_OK) return rc;
     FrameResources& fr = ctx->fr;
-    for (int k = 0; k < kGbSets; ++k) fr.setInFlight[k] = false;
-    fr.syncZeroed[0] = fr.syncZeroed[1] = fr.syncZeroed[2] = false;  // pipelined frames use (and dirty) camCount[0] too
+    for (FrameSet& s : fr.set) s.inFlight = false;
+    fr.syncZeroed[0] = fr.syncZeroed[1] = fr.syncZeroed[2] = false;  // pipelined frames use (and dirty) set 0's block too
     if (!stream) {
         ctx->postStream = nullptr;
         return RT_OK;
     }
-    // sized for the largest frame: with dynamic resolution the current size may be smaller and
-    // grow back later
-    const size_t P = (size_t)ctx->allocW * ctx->allocH;
-#define ALLOC(p, bytes) if (!(p) && (rc = dalloc(ctx, &(p), (bytes))) != RT_OK) return rc
-    for (int k = 1; k < kGbSets; ++k) {  // further G-buffer sets and camera-output slots
-        ALLOC(fr.gColor[k], P * 8);
-        ALLOC(fr.gNormal[k], P * 8);
-        ALLOC(fr.gAlbedo[k], P * 8);
-        ALLOC(fr.gDepth[k], P * 2);
-        ALLOC(fr.gMotion[k], P * 4);
-        if ((rc = alloc_ws_slot(ctx, k, false)) != RT_OK) return rc;
-    }
+    // further G-buffer sets and camera outputs, sized for the largest frame: with dynamic resolution the
+    // current size may be smaller and grow back later
+    for (int k = 1; k < kGbSets; ++k) RT_TRY(alloc_frame_set(ctx, k, false));
     // the shade kernel runs on the side stream, with bounce queues per set ([tuning] shadeOnSide:
     // A/B aid); measured: one GPU 1.025 -> 0.970 ms/frame, one rank's share at
     // 2 / 4 / 8 ranks 0.648 -> 0.650 / 0.495 -> 0.482 / 0.453 -> 0.411 ms
     ctx->shadeOnSide = ctx->tune.shadeOnSide;
-    for (int k = 1; ctx->shadeOnSide && k < kGbSets; ++k)
-        if ((rc = alloc_ws_slot(ctx, k, true)) != RT_OK) return rc;
-#undef ALLOC
-    if ((rc = ensure_bvh_pair(ctx)) != RT_OK) return rc;
-    for (int k = 0; k < kGbSets; ++k) {
-        if (!ctx->camDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->camDone[k], hipEventDisableTiming));
-        if (!ctx->restDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->restDone[k], hipEventDisableTiming));
+    for (int k = 1; ctx->shadeOnSide && k < kGbSets; ++k) RT_TRY(alloc_frame_set(ctx, k, true));
+    RT_TRY(ensure_bvh_pair(ctx));
+    for (FrameSet& s : fr.set) {
+        for (hipEvent_t* e : {&s.camDone, &s.restDone, &s.ptDone, &s.postDone}) RT_TRY(rt_event(ctx, *e));
         if (ctx->tune.resumeSplit == 2) {
-            if (!ctx->leanTraced[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->leanTraced[k], hipEventDisableTiming));
-            if (!ctx->leanDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->leanDone[k], hipEventDisableTiming));
+            RT_TRY(rt_event(ctx, s.leanTraced));
+            RT_TRY(rt_event(ctx, s.leanDone));
         }
-        fr.camInFlight[k] = false;
+        s.camInFlight = false;
     }
-    ctx->bvhInFlight[0] = ctx->bvhInFlight[1] = false;
-    ctx->buildOnSide[0] = ctx->buildOnSide[1] = false;
-    for (int k = 0; k < kGbSets; ++k) {
-        if (!ctx->ptDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ptDone[k], hipEventDisableTiming));
-        if (!ctx->postDone[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->postDone[k], hipEventDisableTiming));
-    }
-    if (!ctx->overlapEv) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->overlapEv, hipEventDisableTiming));
-    if (!ctx->cameraGate) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->cameraGate, hipEventDisableTiming));
+    for (BvhBufs& b : ctx->bvh) b.readInFlight = b.buildOnSide = false;
+    RT_TRY(rt_event(ctx, ctx->overlapEv));
+    RT_TRY(rt_event(ctx, ctx->cameraGate));
     ctx->cameraGated = false;
     // the next frame's camera rays: ungated on one GPU (they run beside this frame's shade and
     // queue-3 traversal), after this frame's trace<3> on two GPUs and its resume<3> on four, where
@@ -1579,8 +1483,7 @@ int rt_set_post_stream(rt_context* ctx, void* stream) {
     ctx->cameraAfter = ctx->stripCount == 1 ? 0 : ctx->stripCount == 2 ? 2 : ctx->stripCount < 8 ? 3 : 1;
     if (ctx->tune.overlapAfter >= 0) ctx->overlapAfter = ctx->tune.overlapAfter;  // [tuning] A/B aids
     if (ctx->tune.cameraAfter >= 0) ctx->cameraAfter = ctx->tune.cameraAfter;
-    if (ctx->tune.resumeSplit == 2 && !ctx->leanStream && (rc = rt_create_stream(ctx, &ctx->leanStream, false)) != RT_OK)
-        return rc;
+    if (ctx->tune.resumeSplit == 2 && !ctx->leanStream) RT_TRY(rt_create_stream(ctx, &ctx->leanStream, false));
     ctx->postStream = (hipStream_t)stream;
     return RT_OK;
 }
@@ -1597,12 +1500,17 @@ int rt_bind_buffer(rt_context* ctx, int name, void* device_ptr, size_t bytes) {
     int rc = sync_streams(ctx, false);
     if (rc != RT_OK) return rc;
     FrameResources& fr = ctx->fr;
+    FrameSet& s = fr.set[set];
     switch (name) {
-        case RT_BUF_RENDER_COLOR: fr.gColor[set] = (uint2*)device_ptr; break;
-        case RT_BUF_NORMAL: fr.gNormal[set] = (uint2*)device_ptr; break;
-        case RT_BUF_ALBEDO: fr.gAlbedo[set] = (uint2*)device_ptr; break;
-        case RT_BUF_DEPTH: fr.gDepth[set] = (uint16_t*)device_ptr; break;
-        case RT_BUF_MOTION: fr.gMotion[set] = (uint32_t*)device_ptr; break;
+        case RT_BUF_RENDER_COLOR:
+            // RenderColorBuffer follows when it is the current set's colour buffer (as in use_frame_set)
+            if (set == fr.gbSet && fr.renderColor == s.color) fr.renderColor = (uint2*)device_ptr;
+            s.color = (uint2*)device_ptr;
+            break;
+        case RT_BUF_NORMAL: s.normal = (uint2*)device_ptr; break;
+        case RT_BUF_ALBEDO: s.albedo = (uint2*)device_ptr; break;
+        case RT_BUF_DEPTH: s.depth = (uint16_t*)device_ptr; break;
+        case RT_BUF_MOTION: s.motion = (uint32_t*)device_ptr; break;
         // the strip-local denoise's exchanged buffers (set 0 only, except the history pair 0 / 1);
         // the new memory takes over the old contents (a frame-persistent state)
         case RT_BUF_ACCUMULATION:
@@ -1624,7 +1532,6 @@ int rt_bind_buffer(rt_context* ctx, int name, void* device_ptr, size_t bytes) {
         default: ctx->err = "rt_bind_buffer: this buffer cannot be bound"; return RT_ERR_ARG;
     }
     fr.gbBound = true;  // synchronous frames then stay in their set (no camera rays traced ahead)
-    if (set == fr.gbSet) select_gbuffers(fr);
     return RT_OK;
 }
 
@@ -1676,10 +1583,10 @@ int rt_get_buffer(const rt_context* cctx, int name, void* dst, size_t bytes) {
         case RT_BUF_SCALED_COLOR: src = fr.scaledColor; break;
         case RT_BUF_NOISE_LEVEL: src = fr.noise8; break;
         case RT_BUF_NOISE_LEVEL16: src = fr.noise16; break;
-        case RT_BUF_NORMAL: src = fr.normal; break;
-        case RT_BUF_ALBEDO: src = fr.albedo; break;
-        case RT_BUF_DEPTH: src = fr.depth; break;
-        case RT_BUF_MOTION: src = fr.motion; break;
+        case RT_BUF_NORMAL: src = fr.cur().normal; break;
+        case RT_BUF_ALBEDO: src = fr.cur().albedo; break;
+        case RT_BUF_DEPTH: src = fr.cur().depth; break;
+        case RT_BUF_MOTION: src = fr.cur().motion; break;
         case RT_BUF_SKY: src = fr.sky; break;
         case RT_BUF_SUN: src = fr.sun; break;
         case RT_BUF_HISTOGRAM: src = fr.histogram; break;
@@ -1809,22 +1716,24 @@ int rt_trace_rays(rt_context* ctx, const float* rays, uint32_t n, float* hits, u
         d[i] = make_float4(rays[8 * i + 4], rays[8 * i + 5], rays[8 * i + 6], 0.0f);
     }
     PathTraceParams p = {};
-    p.triPos = ctx->dTriPos;
-    p.triNrm = ctx->dTriNrm;
-    p.nodes = ctx->dNodes;
-    p.tlasNodes = ctx->dTlasNodes;
+    p.triPos = ctx->lbvh().triPos;
+    p.triNrm = ctx->lbvh().triNrm;
+    p.nodes = ctx->lbvh().nodes;
+    p.tlasNodes = ctx->lbvh().tlasNodes;
     p.ws = fr.ws;
-    p.ws.itersOut = iters ? reinterpret_cast<uint32_t*>(fr.ws.pathL) : nullptr;  // pathL: per-frame scratch
+    bind_workspace(p.ws, fr.set[0], fr.set[0]);  // no shading list: the queue is traced only
+    const PtWorkspace& ws = p.ws;
+    p.ws.itersOut = iters ? reinterpret_cast<uint32_t*>(ws.pathL) : nullptr;  // pathL: per-frame scratch
     if (int rc = sync_streams(ctx)) return rc;  // the queue buffers are shared with in-flight frames
-    HIP_TRY(ctx, hipMemcpyAsync(fr.ws.q3.rayO, o.data(), (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(fr.ws.q3.rayD, d.data(), (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    fr.syncZeroed[0] = false;  // fr.ws.counters is syncCount[0]
-    HIP_TRY(ctx, hipMemsetAsync(fr.ws.counters, 0, kWsCounterWords * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(fr.ws.counters + kCntQ3, &n, 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ws.q3.rayO, o.data(), (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ws.q3.rayD, d.data(), (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    fr.syncZeroed[0] = false;  // set 0's counter block is syncCount[0]
+    HIP_TRY(ctx, hipMemsetAsync(ws.counters, 0, kWsCounterWords * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ws.counters + kCntQ3, &n, 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     HIP_TRY(ctx, rtk_launch_trace_queue(&p, 3, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(hits, fr.ws.hitRec, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(hits, ws.hitRec, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
     if (iters) HIP_TRY(ctx, hipMemcpyAsync(iters, p.ws.itersOut, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
@@ -1834,7 +1743,7 @@ int rt_trace_rays(rt_context* ctx, const float* rays, uint32_t n, float* hits, u
 // Device ray queries (trace_rays.hip): the same traversal for caller rays in device memory, enqueued
 // on the context stream between whatever else the host enqueues there.  Unlike rt_trace_rays it
 // drains nothing, keeps what a synchronous draw traced ahead, and uses none of the path tracer's
-// workspace (fr.ws.counters, the queues, hitRec*, pathL, syncZeroed) nor the ray counter.
+// workspace (the counter blocks, the queues, hitRec*, pathL, syncZeroed) nor the ray counter.
 // Check order: NULL ctx / q, then the other argument checks, then the init state.
 int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q) {
     if (!ctx || !q) return RT_ERR_ARG;
@@ -1852,9 +1761,10 @@ int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q) {
         if (q->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)q->ready_event, 0));
         if (int rc = wait_bvh(ctx)) return rc;  // the current set's build, wherever it ran
         RayQueryParams p;
-        p.nodes = ctx->dNodes;
-        p.tlasNodes = ctx->dTlasNodes;
-        p.triPos = ctx->dTriPos;
+        BvhBufs& b = ctx->lbvh();
+        p.nodes = b.nodes;
+        p.tlasNodes = b.tlasNodes;
+        p.triPos = b.triPos;
         p.org = q->org;
         p.dir = q->dir;
         p.orgStride = q->org_stride;
@@ -1867,14 +1777,13 @@ int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q) {
         // the queue tracers' grid policy (rt_frame_init: cus x tracePerCu, [tuning] tracePerCu)
         HIP_TRY(ctx, rtk_launch_trace_rays(&p, ctx->fr.ws.traceBlocks, (q->flags & RT_QUERY_ANY_HIT) != 0u, s));
         // the set is held against the builds that would overwrite it: a pipelined context's next build
-        // but one (rt_build_bvh waits for bvhFree), a synchronous draw's prebuild (prebuild_next_bvh)
-        const int k = ctx->bvhSet;
+        // but one (rt_build_bvh waits for readDone), a synchronous draw's prebuild (prebuild_next_bvh)
         if (ctx->postStream) {
-            HIP_TRY(ctx, hipEventRecord(ctx->bvhFree[k], s));
-            ctx->bvhInFlight[k] = true;
+            HIP_TRY(ctx, hipEventRecord(b.readDone, s));
+            b.readInFlight = true;
         } else {
-            HIP_TRY(ctx, hipEventRecord(ctx->queryDone[k], s));
-            ctx->queryInFlight[k] = true;
+            HIP_TRY(ctx, hipEventRecord(b.queryDone, s));
+            b.queryInFlight = true;
         }
     }
     if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));

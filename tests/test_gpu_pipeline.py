@@ -284,6 +284,39 @@ def test_serial_counter_blocks_across_mode_switches(rtx, tmp_path):
         assert np.array_equal(a, b), "frame %d" % f
 
 
+def test_frame_sets_across_mode_switches(rtx, tmp_path):
+    """The per-set host state in the order that allocates it piecemeal: two synchronous draws (set 1
+    with its queues, for the camera rays traced ahead), a post stream and three pipelined draws (sets
+    2 and 3, every set's events), no post stream and two synchronous draws (which now alternate the
+    sets the pipelined stretch left current).  After each group the RGBA8 image and the accumulation
+    buffer equal those of a fresh context that drew the same frame numbers synchronously."""
+    import torch
+
+    w, h = 128, 72
+    groups = ((2, None), (3, True), (2, False))  # draws, post stream: keep / set / clear
+
+    def sequence(name, switch):
+        cfg = rtx.write_config(str(tmp_path / (name + ".toml")), w, h, spp=2)
+        rt = rtx.RayTracer(w, h, cfg).init()
+        rt.set_delta_time(16.667)
+        target = torch.zeros(w * h * 4, dtype=torch.uint8, device="cuda:0")
+        post, out = post_stream(), []
+        for draws, pipelined in groups:
+            if switch and pipelined is not None:
+                rt.set_post_stream(post.cuda_stream if pipelined else None)
+            for _ in range(draws):
+                rt.draw_device(target.data_ptr(), 0, asynchronous=bool(switch and pipelined))
+            rt.sync()
+            out.append((target.cpu().numpy().copy(), rt.get_buffer("ACCUMULATION").copy()))
+        rt.cleanup()
+        return out
+
+    ref, got = sequence("one_mode", False), sequence("switched", True)
+    for g, ((rgba0, acc0), (rgba1, acc1)) in enumerate(zip(ref, got)):
+        assert np.array_equal(rgba0, rgba1), "RGBA8 after group %d" % g
+        assert np.array_equal(acc0, acc1), "accumulation after group %d" % g
+
+
 def draw_sequence_plain(rtx, tmp_path, name, w, h, frames):
     import torch
 
