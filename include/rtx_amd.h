@@ -82,8 +82,13 @@ int rt_init(rt_context* ctx);
  * the other G-buffer set ([tuning] syncSpec): the draw still returns with its frame complete, and
  * those kernels may still run on the context's side stream.  The next draw uses their results only
  * when its launch parameters (camera, sky, size, frame number, materials, buffers) and the geometry
- * epoch (rt_update_vertices) equal theirs;
- * any call that waits for the streams (rt_sync, the reads, the setters) discards them first. */
+ * epoch (rt_update_vertices) equal theirs, and traces again otherwise; a change of the sky that
+ * regenerates its tables (skyScalar, sunScalar, sunAngle, timeOfDay, sunAxisAngle, needRegenerate)
+ * always does, also when no launch parameter moves with it (the two scalars);
+ * any call that waits for the streams (rt_sync, the reads, the setters) discards them first.
+ * Parameters only the denoise and post chain read (pass, post, denoise, the frame time) and a device
+ * ray query cost no retrace.  rt_download(RT_ARR_SPEC_STATS) counts the launches, reuses and drops;
+ * tests/test_gpu_draw_state.py walks every state-changing call against this rule. */
 int rt_draw(rt_context* ctx, uint8_t* rgba8_out, float* hdr_out);
 
 /* RayTracer::draw(SurfObj* renderTarget), kernel.cu:259-398 (CopyToOutput kernel.cu:26-59 writes
@@ -748,7 +753,12 @@ int rt_set_hook_stages(rt_context* ctx, uint32_t stage_mask);
  * can all-gather screen strips in place; and the strip-local denoise's exchanged buffers
  * (RT_BUF_ACCUMULATION, RT_BUF_HISTORY_COLOR | RT_BUF_SET1 for the second of the pair,
  * RT_BUF_HISTOGRAM, RT_BUF_RGBA8), whose current contents are copied over.  The memory must
- * outlive the context's use of it. */
+ * outlive the context's use of it.
+ * A G-buffer name carries its set (RT_BUF_SET1..3; none: set 0).  Pipelined frames cycle through all
+ * RT_GBUFFER_SETS sets, so such a host binds every set.  A synchronous context (no post stream) with a
+ * bound G-buffer launches nothing ahead and traces every later frame into set 0, whichever set its
+ * draws had alternated into before the bind: binding set 0 is enough there, and rt_get_info's
+ * gbufferSet reads 0 from the bind on. */
 int rt_bind_buffer(rt_context* ctx, int name, void* device_ptr, size_t bytes);
 
 /* wait for all work on the context stream */
@@ -874,8 +884,14 @@ enum rt_array_name {
     RT_ARR_EMITTER_WEIGHTS = 47, /* float[count] their weights (rt_emitter_weight) */
     RT_ARR_EMITTER_CDF = 48,     /* float[P] the reference Scan (inclusive, block 256) of the weights zero-padded
                                     to P, the power of two >= max(triCount, 256); P from rt_array_bytes */
-    RT_ARR_PT_Q3_BETA = 49       /* float4[cap] step-3 queue: the first diffuse interaction's throughput beta1 xyz,
+    RT_ARR_PT_Q3_BETA = 49,      /* float4[cap] step-3 queue: the first diffuse interaction's throughput beta1 xyz,
                                     ray-cone spread ([0] of RT_ARR_PT_QUEUE are valid) */
+    RT_ARR_SPEC_STATS = 50       /* uint32[4] the synchronous draws' launches ahead (rt_draw), counted on the host
+                                    since rt_init: [0] launched, [1] reused by the next draw, [2] dropped unused
+                                    (the next draw's launch parameters differed, the sky tables were regenerated,
+                                    or a call waited for the streams), [3] 1 while one awaits the next draw;
+                                    [0] == [1] + [2] + [3].  Host state: the read waits for nothing and drops
+                                    nothing.  All zero with [tuning] syncSpec off; pipelined frames add nothing */
 };
 /* RT_ARR_TEX_ALBEDO_AO and RT_ARR_TEX_NORMAL_ROUGHNESS OR-ed with RT_ARR_TEX_SET(k) name the chain of
  * texture set k (k = 0 is the plain name); a k past the context's sets is RT_ERR_ARG (rt_array_bytes: 0). */

@@ -1793,6 +1793,7 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
         case RT_ARR_EMITTER_CDF: return set.emBuilt ? (size_t)set.emCdfLen * 4 : 0;
         case RT_ARR_TRI_MATERIALS: return (size_t)ctx->mesh.triCount;
         case RT_ARR_TRI_MATERIAL_CENSUS: return 256 * sizeof(uint32_t);
+        case RT_ARR_SPEC_STATS: return 4 * sizeof(uint32_t);
         default: return 0;
     }
 }
@@ -1890,6 +1891,13 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
             } else {
                 memcpy(out, ctx->triMatCount, 256 * sizeof(uint32_t));
             }
+            return RT_OK;
+        }
+        case RT_ARR_SPEC_STATS: {  // host counters of the synchronous draws' launches ahead: no wait, nothing dropped
+            if (bytes < 4 * sizeof(uint32_t)) { ctx->err = "destination too small"; return RT_ERR_ARG; }
+            const FrameResources& fr = ctx->fr;
+            const uint32_t v[4] = {fr.specLaunched, fr.specReused, fr.specDropped, fr.spec.valid ? 1u : 0u};
+            memcpy(dst, v, sizeof v);
             return RT_OK;
         }
         default: ctx->err = "unknown array"; return RT_ERR_ARG;

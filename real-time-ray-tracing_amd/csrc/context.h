@@ -173,9 +173,12 @@ struct FrameResources {
         PathTraceParams p{};
     } spec;
     bool specReady = false;          // set 1's buffers and the events exist (ensure_sync_spec)
-    bool gbBound = false;            // a G-buffer is the caller's (rt_bind_buffer): no set rotation
+    bool gbBound = false;            // a G-buffer is the caller's (rt_bind_buffer): no set rotation, synchronous frames in set 0
     unsigned long long* specRayCounter = nullptr;  // the rays of the launches ahead (folded in when used)
     int specCounts = 0;  // specRayCounter holds: 0 nothing, 1 the counts of used launches (to fold), 2 dropped ones
+    // cumulative, host only (RT_ARR_SPEC_STATS): launches ahead made, used by the next draw, and
+    // discarded unused; launched == reused + dropped + (spec.valid ? 1 : 0) at any time
+    uint32_t specLaunched = 0, specReused = 0, specDropped = 0;
     int lastSlot = 0;                  // slot of the last path trace (RT_ARR_PT_Q*)
     // queue 3's length after the last serial path trace, copied to pinned host memory behind it
     // (the fused chain's on/off choice for serial frames)

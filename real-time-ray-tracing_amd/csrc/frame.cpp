@@ -109,6 +109,16 @@ bool sky_params_equal(const rt_sky_params& a, const rt_sky_params& b) {
            a.sunScalar == b.sunScalar && a.sunAngle == b.sunAngle;
 }
 
+// What a synchronous draw traced ahead will not be used: its counter block holds its counts (the next
+// camera launch clears it) and so does specRayCounter (cleared ahead of the next launches).  The
+// caller orders whatever it enqueues next behind specDone, or waits for the side stream.
+void drop_spec(FrameResources& fr) {
+    fr.spec.valid = false;
+    fr.syncZeroed[fr.spec.block] = false;
+    fr.specCounts = 2;
+    ++fr.specDropped;
+}
+
 // kernel.cu:286-307 — regenerate when asked to, or when the sky parameters changed
 int update_sky(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
@@ -116,7 +126,13 @@ int update_sky(rt_context* ctx) {
     const V3 sunDir = sun_direction(sp.timeOfDay, sp.sunAxisAngle);
     fr.sunDir[0] = sunDir.x; fr.sunDir[1] = sunDir.y; fr.sunDir[2] = sunDir.z;
     if (fr.skyValid && !sp.needRegenerate && sky_params_equal(sp, fr.lastSky)) return RT_OK;
-    if (fr.spec.valid) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->specDone, 0));  // they read the sky
+    // The camera and shade kernels traced ahead read the tables rewritten below: the rewrite follows
+    // them, and they are dropped, since the launch parameters hold only the tables' addresses, the sun
+    // direction and its angle (a change of skyScalar or sunScalar alone leaves spec_matches true)
+    if (fr.spec.valid) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->specDone, 0));
+        drop_spec(fr);
+    }
     if (ctx->postStream) {  // frame pipelining: nothing may read the sky while it is rewritten
         const int rc = sync_streams(ctx, false);
         if (rc != RT_OK) return rc;
@@ -330,11 +346,7 @@ int sync_streams(rt_context* ctx, bool report) {
     // camera rays a synchronous draw traced ahead are kept only up to the next draw: any call that
     // waits for the streams (a read, a setter, a mode change) drops them
     FrameResources& fr = ctx->fr;
-    if (fr.spec.valid) {
-        fr.spec.valid = false;
-        fr.syncZeroed[fr.spec.block] = false;
-        fr.specCounts = 2;
-    }
+    if (fr.spec.valid) drop_spec(fr);
     if (fr.specCounts) {  // the ray counts of launches ahead: the used ones into the frame's
         HIP_TRY(ctx, rtk_fold_ray_counts(fr.specCounts == 1 ? fr.rayCounter : nullptr, fr.specRayCounter, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -845,12 +857,20 @@ bool spec_matches(const PathTraceParams& a, uint64_t epochA, uint64_t matA, cons
     // and the tables' buffers are recycled, so triMat's address does not tell its contents: the
     // table's serial does
     if (matA != matB) return false;
+    // emitter sampling: whether a launch samples a list at all selects its kernels and must agree
+    if ((a.emHeader != nullptr) != (b.emHeader != nullptr)) return false;
     PathTraceParams x = a, y = b;
     for (PathTraceParams* q : {&x, &y}) {
         q->rayCounter = nullptr;  // the launches ahead count into specRayCounter
         q->nodes = q->tlasNodes = nullptr;  // the two LBVH sets of one geometry epoch (above)
         q->triPos = nullptr;
         q->triNrm = nullptr;
+        // ... and their emitter lists, which a build writes from its own triangle records and the
+        // material tables: the same list under one epoch and one serial.  Compared by address, a draw
+        // with emitter sampling on would never use what was traced ahead for it
+        q->emHeader = nullptr;
+        q->emTris = nullptr;
+        q->emCdf = nullptr;
         // triDisp stays: launches ahead never carry one (their frame's own path trace came first),
         // and a launch that does must run its motion kernel
         q->ws.traceBlocks = 0;
@@ -962,6 +982,7 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         reuseShade = reuse && fr.spec.shade;
         if (!reuse) p.ws.countersZeroed = 0;  // their counts are in the block: the launcher clears it
         fr.specCounts = reuse ? 1 : 2;  // folded into the frame's (or cleared) ahead of the next ones
+        ++(reuse ? fr.specReused : fr.specDropped);
     }
     if (reuse) {
         for (int k = 0; k < (reuseShade ? 4 : 2) && ctx->ptMarks; ++k)  // zero-length slots for the marks
@@ -1311,6 +1332,7 @@ int launch_spec_camera(rt_context* ctx) {
     }
     fr.syncZeroed[b] = false;
     fr.spec.valid = true;
+    ++fr.specLaunched;
     fr.spec.shade = shade;
     fr.spec.block = b;
     fr.spec.epoch = ctx->geomEpoch;  // of this frame's LBVH, built or checked by enqueue_frame just before
@@ -1532,6 +1554,9 @@ int rt_bind_buffer(rt_context* ctx, int name, void* device_ptr, size_t bytes) {
         default: ctx->err = "rt_bind_buffer: this buffer cannot be bound"; return RT_ERR_ARG;
     }
     fr.gbBound = true;  // synchronous frames then stay in their set (no camera rays traced ahead)
+    // ... and that set is 0, the one a name without a set flag binds: the launches ahead alternated
+    // two sets up to here and may have left the context in set 1, whose buffers are its own
+    if (!ctx->postStream && fr.gbSet != 0) use_frame_set(fr, 0);
     return RT_OK;
 }
 

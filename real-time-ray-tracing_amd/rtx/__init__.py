@@ -28,7 +28,7 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
            BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44, TRI_MATERIAL_CENSUS=45,
-           EMITTER_TRIS=46, EMITTER_WEIGHTS=47, EMITTER_CDF=48, PT_Q3_BETA=49)
+           EMITTER_TRIS=46, EMITTER_WEIGHTS=47, EMITTER_CDF=48, PT_Q3_BETA=49, SPEC_STATS=50)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
