@@ -176,6 +176,9 @@ extern "C" void orc_h2f_n(const uint16_t* h, float* f, size_t n) {
     for (size_t i = 0; i < n; ++i) f[i] = rt_h2f(h[i]);
 }
 
+// the restatement's float -> int conversion (ocommon.h f2i), pinned by tests/test_denoise_synthetic.py
+extern "C" int32_t orc_f2i(float x) { return orc::f2i(x); }
+
 // rt_unorm16 against the IEEE division it replaces, over every 16-bit value: the count of mismatches
 extern "C" int orc_unorm16_mismatches() {
     int bad = 0;

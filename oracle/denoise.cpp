@@ -124,7 +124,7 @@ F3 bicubic_smooth_half(const Img& im, F2 uv) {
     const F2 f3v = {f2.x * f.x, f2.y * f.y};
     const F2 w1 = {f3v.x * -2.0f + f2.x * 3.0f, f3v.y * -2.0f + f2.y * 3.0f};
     const F2 w0 = {1.0f - w1.x, 1.0f - w1.y};
-    const int t0x = (int)fx0, t0y = (int)fy0;
+    const int t0x = f2i(fx0), t0y = f2i(fy0);
     const int sx[4] = {t0x, t0x + 1, t0x, t0x + 1}, sy[4] = {t0y, t0y, t0y + 1, t0y + 1};
     const float wt[4] = {w0.x * w0.y, w1.x * w0.y, w0.x * w1.y, w1.x * w1.y};
     F3 o = f3(0.0f);
@@ -216,7 +216,7 @@ void temporal_filter(const Ctx& c, const uint16_t* in, uint16_t* out, const uint
             float lumaH = cHy.x;
             const float lumaMin = nMin.x, lumaMax = nMax.x, lumaC = ycocg(cV).x;
             float discard = 0.0f;
-            const int hx = (int)floorf(huv.x * (float)c.hW), hy = (int)floorf(huv.y * (float)c.hH);
+            const int hx = f2i(floorf(huv.x * (float)c.hW)), hy = f2i(floorf(huv.y * (float)c.hH));
             for (int i = 0; i < 4; ++i) discard += (mV != acc.u16(hx + i % 2, hy + i / 2, 3)) ? 1.0f : 0.0f;
             discard /= 4.0f;
             cH = cH * (1.0f - discard) + filt * discard;
@@ -429,7 +429,7 @@ void temporal_filter2(const Ctx& c, const uint16_t* in, uint16_t* out, const uin
             float lumaH = cHy.x;
             const float lumaMin = nMin.x, lumaMax = nMax.x, lumaC = ycocg(cV).x;
             float discard = 0.0f;
-            const int hx = (int)floorf(huv.x * (float)c.hW), hy = (int)floorf(huv.y * (float)c.hH);
+            const int hx = f2i(floorf(huv.x * (float)c.hW)), hy = f2i(floorf(huv.y * (float)c.hH));
             for (int i = 0; i < 4; ++i) discard += (mV != (int)hc.u16(hx + i % 2, hy + i / 2, 3)) ? 1.0f : 0.0f;
             discard /= 4.0f;
             if (discard == 1.0f) continue;
@@ -552,7 +552,7 @@ void bicubic_scale(const uint16_t* in, int W, int H, uint16_t* out, int Ws, int 
             const F2 w1 = {1.5f * f3v.x - 2.5f * f2.x + 1.0f, 1.5f * f3v.y - 2.5f * f2.y + 1.0f};
             const F2 w3 = {0.5f * (f3v.x - f2.x), 0.5f * (f3v.y - f2.y)};
             const F2 w2 = {1.0f - w0.x - w1.x - w3.x, 1.0f - w0.y - w1.y - w3.y};
-            const int t1x = (int)fx0, t1y = (int)fy0;
+            const int t1x = f2i(fx0), t1y = f2i(fy0);
             const float wx[4] = {w0.x, w1.x, w2.x, w3.x}, wy[4] = {w0.y, w1.y, w2.y, w3.y};
             F3 o = f3(0.0f);
             float sw = 0.0f;
@@ -694,7 +694,7 @@ F3 catmull_rom(const uint16_t* in, int W, int H, F2 uv) {
     const F2 w1 = {1.5f * f3v.x - 2.5f * f2.x + 1.0f, 1.5f * f3v.y - 2.5f * f2.y + 1.0f};
     const F2 w3 = {0.5f * (f3v.x - f2.x), 0.5f * (f3v.y - f2.y)};
     const F2 w2 = {1.0f - w0.x - w1.x - w3.x, 1.0f - w0.y - w1.y - w3.y};
-    const int t1x = (int)fx0, t1y = (int)fy0;
+    const int t1x = f2i(fx0), t1y = f2i(fy0);
     const float wx[4] = {w0.x, w1.x, w2.x, w3.x}, wy[4] = {w0.y, w1.y, w2.y, w3.y};
     F3 o = f3(0.0f);
     float sw = 0.0f;

@@ -133,6 +133,17 @@ static inline uint32_t sat_u32(float x) {
     return (uint32_t)x;
 }
 
+// CUDA cvt.rzi.s32.f32 semantics, what every float -> int cast of the reference compiles to (and
+// what v_cvt_i32_f32 does on the GPU): truncate toward zero, saturate at INT_MIN / INT_MAX,
+// NaN -> 0.  A plain (int) cast is undefined on the host for NaN and out-of-range values (x86's
+// cvttss2si yields INT_MIN for all of them), so the restatement converts through this.
+static inline int32_t f2i(float x) {
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return INT32_MAX;
+    if (x <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)x;
+}
+
 struct AABB { F3 min, max; };
 static inline AABB aabb_empty() { AABB r = {f3(kFltMax), f3(-kFltMax)}; return r; }
 static inline float aabb_at(const AABB& b, int i) { return i < 3 ? b.min[i] : b.max[i - 3]; }

@@ -106,6 +106,8 @@ def lib() -> C.CDLL:
         L.orc_f2h_n.restype = None
         L.orc_h2f_n.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.orc_h2f_n.restype = None
+        L.orc_f2i.argtypes = [C.c_float]
+        L.orc_f2i.restype = C.c_int32
         L.orc_scene_generate.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]
         L.orc_scene_generate.restype = C.c_int
@@ -229,6 +231,12 @@ def h2f(h: np.ndarray) -> np.ndarray:
     f = np.empty(h.shape, np.float32)
     lib().orc_h2f_n(h.ctypes.data, f.ctypes.data, h.size)
     return f
+
+
+def f2i(x: float) -> int:
+    """ocommon.h f2i, the restatement's float -> int conversion (cvt.rzi.s32.f32: truncate, saturate,
+    NaN -> 0)."""
+    return lib().orc_f2i(x)
 
 
 # ---------------------------------------------------------------- sky (oracle/sky.cpp)

@@ -134,7 +134,7 @@ static F4 bicubic_smoothstep_tex(const uint16_t* tex, int level, F2 uv) {
     F2 f3v = {f2.x * f.x, f2.y * f.y};
     F2 w1 = {f3v.x * -2.0f + f2.x * 3.0f, f3v.y * -2.0f + f2.y * 3.0f};
     F2 w0 = {1.0f - w1.x, 1.0f - w1.y};
-    int t0x = (int)floorf(UV.x - 0.5f), t0y = (int)floorf(UV.y - 0.5f);
+    int t0x = f2i(floorf(UV.x - 0.5f)), t0y = f2i(floorf(UV.y - 0.5f));
     int t1x = t0x + 1, t1y = t0y + 1;
     int sx[4] = {t0x, t1x, t0x, t1x}, sy[4] = {t0y, t0y, t1y, t1y};
     float wts[4] = {w0.x * w0.y, w1.x * w0.y, w0.x * w1.y, w1.x * w1.y};
@@ -192,7 +192,7 @@ static F3 bicubic_smoothstep_env(Fetch fetch, F2 uv, int W, int H) {
     F2 f3v = {f2.x * f.x, f2.y * f.y};
     F2 w1 = {f3v.x * -2.0f + f2.x * 3.0f, f3v.y * -2.0f + f2.y * 3.0f};
     F2 w0 = {1.0f - w1.x, 1.0f - w1.y};
-    int t0x = (int)floorf(UV.x - 0.5f), t0y = (int)floorf(UV.y - 0.5f);
+    int t0x = f2i(floorf(UV.x - 0.5f)), t0y = f2i(floorf(UV.y - 0.5f));
     int sx[4] = {t0x, t0x + 1, t0x, t0x + 1}, sy[4] = {t0y, t0y, t0y + 1, t0y + 1};
     float wts[4] = {w0.x * w0.y, w1.x * w0.y, w0.x * w1.y, w1.x * w1.y};
     F3 o = f3(0.0f);

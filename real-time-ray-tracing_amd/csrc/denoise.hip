@@ -1214,8 +1214,15 @@ RT_DEV uint2 temporal2_pixel(const DenoisePostParams& P, const uint2* in, int x,
     const F2 uv = {((float)x + 0.5f) * inv.x, ((float)y + 0.5f) * inv.y};
     const F2 huv = {uv.x + mv.x, uv.y + mv.y};
     const bool onScreen = !(huv.x < 0 || huv.y < 0 || huv.x > 1.0f || huv.y > 1.0f);
-    const SmoothTaps ht = smooth_taps(hc, huv);  // clamped reads: safe off screen too
-    const int hx = (int)floorf(huv.x * (float)hc.W), hy = (int)floorf(huv.y * (float)hc.H);
+    // Off screen the history is not used, and its texels are read at the pixel's own position.  At
+    // huv itself they would not be safe: the first texel is (int)floorf(huv * size - 0.5f), INT_MAX
+    // for a motion of +Inf (the conversion saturates), the second texel's `+ 1` then overflows, and
+    // the compiled clamp compares the first texel (no overflow assumed) but takes the minimum of
+    // the wrapped sum: texel INT_MIN, far outside the buffer.  On screen huv is in [0, 1] or NaN
+    // (texel 0), so the sums stay in range.
+    const F2 hs = {onScreen ? huv.x : uv.x, onScreen ? huv.y : uv.y};
+    const SmoothTaps ht = smooth_taps(hc, hs);
+    const int hx = (int)floorf(hs.x * (float)hc.W), hy = (int)floorf(hs.y * (float)hc.H);
     uint2 hq[4];
     uint32_t hm[4];
 #pragma unroll
