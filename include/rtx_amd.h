@@ -271,6 +271,76 @@ int rt_set_material_textures(rt_context* ctx, uint32_t first_id, uint32_t count,
 int rt_get_material_textures(const rt_context* ctx, uint32_t first_id, uint32_t count, uint8_t* sets);
 int rt_reset_material_textures(rt_context* ctx);
 
+/* Sky sets and environment maps.
+ *
+ * A sky set is everything one sky generation writes: the 512 x 256 sky table with its pdf, CDF and
+ * probe tree, the 32 x 32 sun tables likewise, and the light-selection terms (about 3.2 MB).  [scene]
+ * skySets = N (absent, 0 or 1: one set; at most RT_SKY_SETS_MAX) makes the context hold N of them.  An
+ * unparsable or negative value: RT_ERR_IO from rt_create; N > 8: RT_ERR_ARG from rt_init, before any
+ * device call.  With one set a change of the sky parameters rewrites the tables in place, which on a
+ * pipelined context (rt_set_post_stream) waits for every stream first.  With two or more it never
+ * waits on the host and drains no stream: the next set in turn is generated behind its own readers,
+ * which are waited for on the device, on the side stream of a pipelined context (where the LBVH builds
+ * and the camera kernels run) and on the context stream otherwise; path traces enqueued earlier, the
+ * pipelined frames in flight and what a synchronous draw traced ahead, keep the set they were launched
+ * with, and a launch ahead made under the old sky is traced again (RT_ARR_SPEC_STATS[2] counts it).
+ *
+ * An environment replaces the Hosek sky table and its pdf by an image of the caller's; the sun tables
+ * stay those of the sky parameters (sunScalar, sunAngle, timeOfDay, sunAxisAngle), and the CDF, the
+ * probe trees and the light selection are derived as ever.  The sky has an upper hemisphere only: the
+ * lookup clamps below the horizon and blends to the mist, with or without an environment.  An all-zero
+ * environment is valid: every light sample then goes to the sun.  A later change of the sky parameters
+ * regenerates the sun tables and keeps the environment.
+ *
+ * The image: width x height texels of four floats (RT_ENV_FORMAT_F32X4) or four halves
+ * (RT_ENV_FORMAT_F16X4), alpha ignored.  RT_ENV_LAYOUT_TABLE is the renderer's own equal-area table,
+ * 512 x 256 (what RT_BUF_SKY returns).  RT_ENV_LAYOUT_LATLONG is a latitude-longitude image, row 0 at
+ * the zenith, 4 <= width <= 16384, 2 <= height <= 16384, of which the rows above the horizon (2 r + 1 <
+ * height) are read; column c points along the table's own azimuth u = (c + 0.5) / width.
+ * rt_environment_table is the definition of the table an image gives, compiled for the host, with no
+ * context and no device; the device gives its bits.  In short: a source value x counts as
+ * (x == x && x > 0) ? min(x, 65504) : 0; a LATLONG texel belongs to the table cell its centre falls
+ * into (column (2 c + 1) * 256 / width; row min(255, (int)(cos(theta_r) * 256)), theta_r = pi (2 r + 1)
+ * / (2 height)), a cell's value is the mean of its texels weighted by sin(theta_r), summed in fp32 in
+ * ascending column, then row order, and a cell that owns no column or row takes the nearest one; the
+ * result times `scale`, at most 65504; pdf = dot(rgb, (0.3, 0.6, 0.1)) as the Hosek table's.
+ * table: 131072 x 4 floats (.w = 0), pdf: 131072 floats.
+ *
+ * rt_set_environment behaves like the other host setters: it waits for the renderer's streams, drops
+ * what a synchronous draw traced ahead, copies the image into staging of its own (the caller's array
+ * is free on return) and takes effect for every path trace enqueued afterwards; it works at any
+ * skySets.  rt_set_environment_device is the stream-ordered counterpart, in the family of
+ * rt_update_vertices_device: it needs skySets >= 2; the host is never synchronised and no stream is
+ * drained; `texels` is device memory, read after ready_event (NULL: after everything enqueued on the
+ * context stream so far), and work enqueued on the context stream after the call follows that read;
+ * frames in flight keep their sky.  The first device set of a context, and the first one of a larger
+ * LATLONG image than any before, allocates device scratch.  rt_reset_environment is a host-style setter
+ * that goes back to the Hosek table.  rt_get_environment: whether an environment is active.
+ *
+ * Checked in this order, and on an error nothing changes: RT_ERR_ARG for NULL ctx or struct, NULL
+ * texels, an unknown format or layout, a size outside the limits (TABLE: not 512 x 256), a scale that
+ * is not finite or <= 0, a misaligned device pointer (16 B for F32X4, 8 B for F16X4); RT_ERR_STATE
+ * before rt_init, or for the device variant with one sky set; RT_ERR_HIP for a failed launch.  Never
+ * RT_ERR_DEVICE.  Every rank of a multi-GPU run calls with the same data. */
+#define RT_SKY_SETS_MAX 8
+int rt_get_sky_sets(const rt_context* ctx, uint32_t* count);
+#define RT_ENV_FORMAT_F32X4 0
+#define RT_ENV_FORMAT_F16X4 1
+#define RT_ENV_LAYOUT_TABLE   0  /* 512 x 256, the renderer's own equal-area table (RT_BUF_SKY) */
+#define RT_ENV_LAYOUT_LATLONG 1  /* width x height latitude-longitude image, row 0 at the zenith */
+typedef struct rt_environment {
+    const void* texels;
+    uint32_t width, height, format, layout;
+    float scale;        /* multiplies the radiance, like skyScalar; finite, > 0 */
+    void* ready_event;  /* device variant: hipEvent_t or NULL, as in rt_update_vertices_device */
+} rt_environment;
+int rt_set_environment(rt_context* ctx, const rt_environment* host);
+int rt_set_environment_device(rt_context* ctx, const rt_environment* dev);
+int rt_reset_environment(rt_context* ctx);
+int rt_get_environment(const rt_context* ctx, int* active);
+/* the rule, compiled for the host; no context, no device */
+int rt_environment_table(const rt_environment* host, float* table /*131072 x 4*/, float* pdf /*131072*/);
+
 /* Scene input (host only, no device needed): Perlin::noise3D (perlin.h:50-78) with the reference
  * permutation, the source of the procedural terrain's voxel heights (Chunk::Generate,
  * terrain.cpp:5-45), at n points (xyz triples). */
@@ -768,8 +838,9 @@ int rt_sync(rt_context* ctx);
  * (0 = BVH build, 1 = primary rays, 2 = path trace, 3 = full frame: BVH + path trace + denoise
  * + post, 4 = denoise + post, 5 = a whole-mesh vertex update with its smooth normals, fed the
  * current positions from a copy: arrays and epoch stay as they are, 6 = a whole-mesh set (rt_set_mesh_device)
- * fed the current mesh from a copy, arrays and epoch likewise left as they are) and returns the total
- * milliseconds between the first launch and the end of the last. */
+ * fed the current mesh from a copy, arrays and epoch likewise left as they are, 7 = one sky-set
+ * generation into a spare set, under the environment when one is active, the current set and its serial
+ * left as they are) and returns the total milliseconds between the first launch and the end of the last. */
 int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms);
 
 /* Stage 6 split by HIP events between its launches: `iters` whole-mesh sets one after the other,

@@ -407,6 +407,16 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
         }
         ctx->textureSets = (int)n;
     }
+    if (const rttoml::Value* v = rttoml::find(doc, "scene", "skySets")) {  // a count, 0 = 1; the limit is rt_init's
+        char* end = nullptr;
+        const long long n = v->isArray || v->isString || v->raw.empty() ? -1 : strtoll(v->raw.c_str(), &end, 10);
+        if (n < 0 || n > 0x7FFFFFFFll || !end || *end != '\0') {
+            g_createError = "config parse error: [scene] skySets must be a count";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->skySetsCfg = (int)n;
+    }
     ctx->spp = rttoml::find_or_int(doc, "render", "spp", 1);
     ctx->bvhThreads = rttoml::find_or_int(doc, "render", "bvhThreads", 0);  // LBVH workgroup shape (A/B, tests)
     ctx->device = rttoml::find_or_int(doc, "render", "device", -1);
@@ -510,6 +520,11 @@ int rt_init(rt_context* ctx) {
         return RT_ERR_ARG;
     }
     ctx->texSets = ctx->textureSets > 0 ? (uint32_t)ctx->textureSets : 1u;
+    if (ctx->skySetsCfg > RT_SKY_SETS_MAX) {
+        ctx->err = "[scene] skySets out of range: at most " + std::to_string(RT_SKY_SETS_MAX);
+        return RT_ERR_ARG;
+    }
+    ctx->skySets = ctx->skySetsCfg > 0 ? ctx->skySetsCfg : 1;
     // ---- scene (init.cu:78-130), built and checked on the host before any device call, so a bad
     // input is reported as such on any machine
     std::string err;
@@ -650,6 +665,7 @@ void rt_destroy(rt_context* ctx) {
     if (ctx->leanStream) (void)hipStreamDestroy(ctx->leanStream);
     if (ctx->ownPostStream) (void)hipStreamDestroy(ctx->ownPostStream);
     for (void* p : ctx->allocations) (void)hipFree(p);
+    if (ctx->envStage) (void)hipFree(ctx->envStage);  // rt_set_environment's staging, regrown outside the list
     if (ctx->fr.q3Host) (void)hipHostFree(ctx->fr.q3Host);
     if (ctx->status) (void)hipHostFree(ctx->status);
     if (ctx->ownStream) {
@@ -1441,6 +1457,12 @@ int rt_reset_materials(rt_context* ctx) {
 
 // ---------------------------------------------------------------- texture-set binding
 
+int rt_get_sky_sets(const rt_context* ctx, uint32_t* count) {
+    if (!ctx || !count) return RT_ERR_ARG;
+    *count = ctx->inited ? (uint32_t)ctx->skySets : (ctx->skySetsCfg > 0 ? (uint32_t)ctx->skySetsCfg : 1u);
+    return RT_OK;
+}
+
 int rt_get_texture_sets(const rt_context* ctx, uint32_t* count) {
     if (!ctx || !count) return RT_ERR_ARG;
     *count = ctx->inited ? ctx->texSets : (ctx->textureSets > 0 ? (uint32_t)ctx->textureSets : 1u);
@@ -1557,10 +1579,17 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
             HIP_TRY(ctx, hipMemcpy(ctx->dIdxStage, ctx->dIdx, (size_t)ctx->mesh.triCount * 12, hipMemcpyDeviceToDevice));
         HIP_TRY(ctx, hipDeviceSynchronize());
     }
+    if (stage == 7) {  // nothing reads the spare set: the streams idle, and the spare allocated ahead of the timing
+        int rc = sync_streams(ctx, false);
+        if (rc == RT_OK) rc = rt_time_sky_generation(ctx);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (int i = 0; i < iters; ++i) {
         int rc = RT_OK;
         if (stage == 0) rc = rt_build_bvh(ctx);
+        else if (stage == 7) rc = rt_time_sky_generation(ctx);
         else if (stage == 5) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false);
         else if (stage == 6) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false, &same);
         else if (stage == 1) rc = rt_trace_primary(ctx, 1 + i, 0);
@@ -1838,10 +1867,10 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_HIT_FAKE_NORMALS: src = ctx->dHitFake; break;
         case RT_ARR_HIT_STATS: src = ctx->dHitStats; break;
         case RT_ARR_RAYS: src = ctx->fr.rays; break;
-        case RT_ARR_SKY_PDF: src = ctx->fr.skyPdf; break;
-        case RT_ARR_SKY_CDF: src = ctx->fr.skyCdf; break;
-        case RT_ARR_SUN_PDF: src = ctx->fr.sunPdf; break;
-        case RT_ARR_SUN_CDF: src = ctx->fr.sunCdf; break;
+        case RT_ARR_SKY_PDF: src = ctx->fr.sky().skyPdf; break;
+        case RT_ARR_SKY_CDF: src = ctx->fr.sky().skyCdf; break;
+        case RT_ARR_SUN_PDF: src = ctx->fr.sky().sunPdf; break;
+        case RT_ARR_SUN_CDF: src = ctx->fr.sky().sunCdf; break;
         case RT_ARR_HISTOGRAM: src = ctx->fr.histogram; break;
         case RT_ARR_EXPOSURE: src = ctx->fr.exposure; break;
         case RT_ARR_COLOR4: src = ctx->fr.c4; break;
@@ -1868,7 +1897,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
             if (bytes < 16) { ctx->err = "destination too small"; return RT_ERR_ARG; }
             float* o = (float*)dst;
             memcpy(o, ctx->fr.sunDir, 12);
-            o[3] = ctx->fr.cosThetaMax;
+            o[3] = ctx->fr.sky().cosThetaMax;
             return RT_OK;
         }
         case RT_ARR_TRI_MATERIALS: {  // what the kernels read; without a table the reference's, 3 everywhere

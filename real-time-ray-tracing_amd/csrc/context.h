@@ -116,26 +116,43 @@ struct FrameSet {
     hipEvent_t leanTraced = nullptr, leanDone = nullptr;  // fork and join of the split resume<3>'s lean pass
 };
 
-struct FrameResources {
-    bool ready = false;
-    // sky / sun (kernel.cu:280-307)
-    float* solar = nullptr;
-    float* limb = nullptr;
-    float* cie = nullptr;
+// Sky sets (rt_context::skySets): everything one sky generation (rtk_launch_sky) writes,
+// the host values that belong to those tables, and the events that order the set's next writer behind
+// its readers.  Launches hold their set's addresses by value, so with two sets or more update_sky never
+// rewrites the current set: it generates into the next one in turn, behind these events (waited for on
+// the device), and makes it current.  With one set the tables are rewritten in place behind host waits.
+constexpr int kSkySetsMax = RT_SKY_SETS_MAX;
+struct SkySet {
     float4* sky = nullptr;
     float* skyPdf = nullptr;
     float* skyCdf = nullptr;
     float4* sun = nullptr;
     float* sunPdf = nullptr;
     float* sunCdf = nullptr;
-    float* scanSums = nullptr;
     float* skyTree = nullptr;   // light-CDF probe heaps (kSkyTreeNodes / kSunTreeNodes)
     float* sunTree = nullptr;
-    float* lightSel = nullptr;   // [4] SampleLight's per-frame terms (k_light_select)
+    float* lightSel = nullptr;  // [4] SampleLight's per-frame terms (k_light_select)
+    float cosThetaMax = 1.0f, sunArea = 0.0f;
+    hipEvent_t read = nullptr;      // behind the last path trace that read it, on the context stream
+    hipEvent_t specRead = nullptr;  // behind the last kernels a synchronous draw launched ahead on it (side stream)
+    bool readValid = false, specValid = false;
+};
+
+struct FrameResources {
+    bool ready = false;
+    // sky / sun (kernel.cu:280-307)
+    float* solar = nullptr;
+    float* limb = nullptr;
+    float* cie = nullptr;
+    SkySet skySet[kSkySetsMax];  // [rt_context::skySets]; skySet[skyCur] is what the next launch reads
+    int skyCur = 0;
+    SkySet& sky() { return skySet[skyCur]; }
+    const SkySet& sky() const { return skySet[skyCur]; }
+    uint64_t skySerial = 0;      // +1 per change of the current set (spec_matches: addresses are recycled)
+    float* scanSums = nullptr;
     bool skyValid = false;
     rt_sky_params lastSky{};
     float sunDir[3] = {0, 1, 0};
-    float cosThetaMax = 1.0f, sunArea = 0.0f;
     // soil textures (init.cu:524-577)
     uint2* texAlbedo = nullptr;
     uint2* texNormal = nullptr;
@@ -170,6 +187,7 @@ struct FrameResources {
         int block = 0;
         uint64_t epoch = 0;  // the geometry epoch of the LBVH they were traced on
         uint64_t matSerial = 0;  // rt_context::matSerial of the material table they read
+        uint64_t skySerial = 0;  // FrameResources::skySerial of the sky set they read
         PathTraceParams p{};
     } spec;
     bool specReady = false;          // set 1's buffers and the events exist (ensure_sync_spec)
@@ -413,6 +431,25 @@ struct rt_context {
     // rt_upload_texture_set_device writes a set in place on the context stream: it waits there for what
     // the other streams hold so far (texSide / texLean, recorded at the call) and they wait for texDone
     hipEvent_t texSide = nullptr, texLean = nullptr, texDone = nullptr;
+    // sky sets and environment maps.  skySets: the sets the context holds.  The
+    // environment is one context-owned table with its pdf (envTable / envPdf, written by the ingest,
+    // environment.hip); while envActive, generating a sky set copies it where k_sky would run.  Every
+    // write of a sky set and of the environment table runs on one stream (sky_stream()), so the table
+    // needs no events of its own.
+    int skySetsCfg = 0;                 // [scene] skySets as parsed (0: absent); checked by rt_init
+    int skySets = 1;
+    bool envActive = false;
+    float4* envTable = nullptr;         // [kSkySize], allocated by the first rt_set_environment*
+    float* envPdf = nullptr;
+    int* envRowY = nullptr;             // the LATLONG ingest's scratch (EnvIngestParams)
+    float* envRowW = nullptr;
+    uint32_t* envRuns = nullptr;
+    float4* envRowSums = nullptr;
+    size_t envRowSumsRows = 0;          // rows envRowSums holds
+    void* envStage = nullptr;           // rt_set_environment's copy of the caller's image
+    size_t envStageBytes = 0;
+    hipEvent_t envSrc = nullptr;        // the context stream's work up to a device set without a ready event
+    hipEvent_t envDone = nullptr;       // the last device set's end
     // device ray queries (rt_trace_rays_device, trace_rays.hip): the kernel's fetch counters (kParts,
     // 64 B apart; zeroed on the context stream ahead of each launch: queries on one stream serialise,
     // and the setters that change the stream drain it)
@@ -491,6 +528,11 @@ int rt_event(rt_context* ctx, hipEvent_t& e, bool timing = false);  // context.c
 int rt_create_stream(rt_context* ctx, hipStream_t* s, bool high);  // context.cpp: renderer streams
 extern "C" int ensure_bvh_pair(rt_context* ctx);  // frame.cpp: second LBVH set, side stream, build events
 int rt_frame_init(rt_context* ctx);  // frame.cpp: sky tables, textures, G-buffers
+int rt_time_sky_generation(rt_context* ctx);  // frame.cpp: rt_time_stage(7)'s launch, one generation into a spare sky set
+int rt_regenerate_sky(rt_context* ctx);  // frame.cpp: the sky tables again from the current parameters and environment
+// the stream every sky-set and environment-table write runs on: the side stream of a pipelined context,
+// where the builds and camera kernels run, and the context stream otherwise (DESIGN.md §3.1's choice)
+inline hipStream_t sky_stream(const rt_context* ctx) { return ctx->postStream ? ctx->sideStream : ctx->stream; }
 int sync_streams(rt_context* ctx, bool report = true);  // frame.cpp: context, post and side streams (report: RT_ERR_DEVICE)
 void poll_q3(rt_context* ctx);       // frame.cpp: the last serial frame's queue-3 length, if stored
 int check_device_status(rt_context* ctx);  // frame.cpp: kernel failure reports (RT_ERR_DEVICE)

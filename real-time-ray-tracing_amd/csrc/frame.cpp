@@ -67,17 +67,22 @@ V3 sun_direction(float timeOfDay, float sunAxisAngle) {
     return normalize(r.v);
 }
 
-float fitting(const float* m, float s, int i) {  // GetFittingData (sky.cuh:90-99)
-    return (rt_powf(1.0f - s, 5.0f) * m[i] + 5.0f * rt_powf(1.0f - s, 4.0f) * s * m[i + 9] +
-            10.0f * rt_powf(1.0f - s, 3.0f) * rt_powf(s, 2.0f) * m[i + 18] +
-            10.0f * rt_powf(1.0f - s, 2.0f) * rt_powf(s, 3.0f) * m[i + 27] +
-            5.0f * (1.0f - s) * rt_powf(s, 4.0f) * m[i + 36] + rt_powf(s, 5.0f) * m[i + 45]);
+// GetFittingData / GetFittingData2 (sky.cuh:90-111): the quintic Bernstein blend of six datasets at
+// s.  The six weights depend on s alone, so a sky generation evaluates them once for its 100 blends
+// instead of eleven rt_powf per blend (84 us of host time per sky change): each weight is the very
+// prefix of the reference's term, in its association, so every blend has the reference's bits.
+struct SkyFit { float w[6]; };
+SkyFit sky_fit(float s) {
+    return SkyFit{{rt_powf(1.0f - s, 5.0f), 5.0f * rt_powf(1.0f - s, 4.0f) * s,
+                   10.0f * rt_powf(1.0f - s, 3.0f) * rt_powf(s, 2.0f), 10.0f * rt_powf(1.0f - s, 2.0f) * rt_powf(s, 3.0f),
+                   5.0f * (1.0f - s) * rt_powf(s, 4.0f), rt_powf(s, 5.0f)}};
 }
-float fitting2(const float* m, float s) {  // GetFittingData2 (sky.cuh:102-111)
-    return (rt_powf(1.0f - s, 5.0f) * m[0] + 5.0f * rt_powf(1.0f - s, 4.0f) * s * m[1] +
-            10.0f * rt_powf(1.0f - s, 3.0f) * rt_powf(s, 2.0f) * m[2] +
-            10.0f * rt_powf(1.0f - s, 2.0f) * rt_powf(s, 3.0f) * m[3] + 5.0f * (1.0f - s) * rt_powf(s, 4.0f) * m[4] +
-            rt_powf(s, 5.0f) * m[5]);
+float fitting(const float* m, const SkyFit& f, int i) {  // GetFittingData (sky.cuh:90-99)
+    return (f.w[0] * m[i] + f.w[1] * m[i + 9] + f.w[2] * m[i + 18] + f.w[3] * m[i + 27] + f.w[4] * m[i + 36] +
+            f.w[5] * m[i + 45]);
+}
+float fitting2(const float* m, const SkyFit& f) {  // GetFittingData2 (sky.cuh:102-111)
+    return (f.w[0] * m[0] + f.w[1] * m[1] + f.w[2] * m[2] + f.w[3] * m[3] + f.w[4] * m[4] + f.w[5] * m[5]);
 }
 
 struct SkyTablesHost {
@@ -119,34 +124,20 @@ void drop_spec(FrameResources& fr) {
     ++fr.specDropped;
 }
 
-// kernel.cu:286-307 — regenerate when asked to, or when the sky parameters changed
-int update_sky(rt_context* ctx) {
+// One generation of the sky tables into `dst` on stream s (kernel.cu:286-307), from the clamped sky
+// parameters; under an environment (rt_set_environment) the sky table and its pdf are copies of the
+// context's environment table instead of k_sky's output, the sun tables and everything derived as ever
+int generate_sky(rt_context* ctx, SkySet& dst, hipStream_t s) {
     FrameResources& fr = ctx->fr;
-    rt_sky_params& sp = ctx->params.sky;
-    const V3 sunDir = sun_direction(sp.timeOfDay, sp.sunAxisAngle);
-    fr.sunDir[0] = sunDir.x; fr.sunDir[1] = sunDir.y; fr.sunDir[2] = sunDir.z;
-    if (fr.skyValid && !sp.needRegenerate && sky_params_equal(sp, fr.lastSky)) return RT_OK;
-    // The camera and shade kernels traced ahead read the tables rewritten below: the rewrite follows
-    // them, and they are dropped, since the launch parameters hold only the tables' addresses, the sun
-    // direction and its angle (a change of skyScalar or sunScalar alone leaves spec_matches true)
-    if (fr.spec.valid) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->specDone, 0));
-        drop_spec(fr);
-    }
-    if (ctx->postStream) {  // frame pipelining: nothing may read the sky while it is rewritten
-        const int rc = sync_streams(ctx, false);
-        if (rc != RT_OK) return rc;
-    }
-    sp.sunScalar = sp.sunScalar > 0.00001f ? sp.sunScalar : 0.00001f;
-    sp.skyScalar = sp.skyScalar > 0.00001f ? sp.skyScalar : 0.00001f;
-    sp.sunAngle = sp.sunAngle > 0.51f ? sp.sunAngle : 0.51f;
+    const rt_sky_params& sp = ctx->params.sky;
+    const V3 sunDir = v3(fr.sunDir[0], fr.sunDir[1], fr.sunDir[2]);
     SkyGenParams p;
     memcpy(p.sunDir, fr.sunDir, 12);
     p.skyScalar = sp.skyScalar;
     p.sunScalar = sp.sunScalar;
     p.sunAngle = sp.sunAngle;
     const float elevation = rt_acosf(sunDir.y);
-    const float se = rt_powf(elevation / (kPi / 2.0f), (1.0f / 3.0f));
+    const SkyFit se = sky_fit(rt_powf(elevation / (kPi / 2.0f), (1.0f / 3.0f)));
     for (int ch = 0; ch < 10; ++ch) {
         for (int i = 0; i < 9; ++i) p.st.configs[ch * 9 + i] = fitting(g_tables.skyDataSets.data() + ch * 54, se, i);
         p.st.radiances[ch] = fitting2(g_tables.skyDataSetsRad.data() + ch * 6, se);
@@ -156,20 +147,67 @@ int update_sky(rt_context* ctx) {
     p.solar = fr.solar;
     p.limb = fr.limb;
     p.cie = fr.cie;
-    p.skyBuffer = fr.sky;
-    p.skyPdf = fr.skyPdf;
-    p.skyCdf = fr.skyCdf;
-    p.sunBuffer = fr.sun;
-    p.sunPdf = fr.sunPdf;
-    p.sunCdf = fr.sunCdf;
+    p.skyBuffer = dst.sky;
+    p.skyPdf = dst.skyPdf;
+    p.skyCdf = dst.skyCdf;
+    p.sunBuffer = dst.sun;
+    p.sunPdf = dst.sunPdf;
+    p.sunCdf = dst.sunCdf;
     p.scanSums = fr.scanSums;
-    p.skyTree = fr.skyTree;
-    p.sunTree = fr.sunTree;
-    p.lightSel = fr.lightSel;
-    HIP_TRY(ctx, rtk_launch_sky(&p, ctx->stream));
-    if (ctx->postStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // before the side stream's camera rays
-    fr.sunArea = rt_powf(rt_tanf(sunRadius), 2.0f) * kPi;
-    fr.cosThetaMax = p.cosThetaMax;
+    p.skyTree = dst.skyTree;
+    p.sunTree = dst.sunTree;
+    p.lightSel = dst.lightSel;
+    if (ctx->envActive) HIP_TRY(ctx, rtk_launch_sky_env(&p, ctx->envTable, ctx->envPdf, s));
+    else HIP_TRY(ctx, rtk_launch_sky(&p, s));
+    dst.sunArea = rt_powf(rt_tanf(sunRadius), 2.0f) * kPi;
+    dst.cosThetaMax = p.cosThetaMax;
+    return RT_OK;
+}
+
+void clamp_sky_params(rt_sky_params& sp) {  // kernel.cu:291-293
+    sp.sunScalar = sp.sunScalar > 0.00001f ? sp.sunScalar : 0.00001f;
+    sp.skyScalar = sp.skyScalar > 0.00001f ? sp.skyScalar : 0.00001f;
+    sp.sunAngle = sp.sunAngle > 0.51f ? sp.sunAngle : 0.51f;
+}
+
+// kernel.cu:286-307 — regenerate when asked to, or when the sky parameters changed
+int update_sky(rt_context* ctx) {
+    FrameResources& fr = ctx->fr;
+    rt_sky_params& sp = ctx->params.sky;
+    const V3 sunDir = sun_direction(sp.timeOfDay, sp.sunAxisAngle);
+    fr.sunDir[0] = sunDir.x; fr.sunDir[1] = sunDir.y; fr.sunDir[2] = sunDir.z;
+    if (fr.skyValid && !sp.needRegenerate && sky_params_equal(sp, fr.lastSky)) return RT_OK;
+    if (ctx->skySets > 1) {
+        // Sky sets: the next set in turn, generated on the sky stream behind that
+        // set's readers, which are waited for on the device; no host wait and no stream drained.  What
+        // was launched earlier keeps the set it was launched with: pipelined frames in flight, and what
+        // a synchronous draw traced ahead, which the next path trace drops by the serial (spec_matches).
+        hipStream_t s = sky_stream(ctx);
+        const int next = (fr.skyCur + 1) % ctx->skySets;
+        SkySet& dst = fr.skySet[next];
+        if (dst.readValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.read, 0));
+        if (dst.specValid) HIP_TRY(ctx, hipStreamWaitEvent(s, dst.specRead, 0));
+        clamp_sky_params(sp);
+        RT_TRY(generate_sky(ctx, dst, s));
+        dst.readValid = dst.specValid = false;
+        fr.skyCur = next;
+    } else {
+        // The camera and shade kernels traced ahead read the tables rewritten below: the rewrite follows
+        // them, and they are dropped, since the launch parameters hold only the tables' addresses, the sun
+        // direction and its angle (a change of skyScalar or sunScalar alone leaves spec_matches true)
+        if (fr.spec.valid) {
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->specDone, 0));
+            drop_spec(fr);
+        }
+        if (ctx->postStream) {  // frame pipelining: nothing may read the sky while it is rewritten
+            const int rc = sync_streams(ctx, false);
+            if (rc != RT_OK) return rc;
+        }
+        clamp_sky_params(sp);
+        RT_TRY(generate_sky(ctx, fr.sky(), ctx->stream));
+        if (ctx->postStream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // before the side stream's camera rays
+    }
+    ++fr.skySerial;
     fr.skyValid = true;
     sp.needRegenerate = 0;
     fr.lastSky = sp;
@@ -482,6 +520,38 @@ static int alloc_frame_set(rt_context* ctx, int k, bool queues) {
     return RT_OK;
 }
 
+// Sky set k's tables and events (set 0's tables are rt_frame_init's)
+static int alloc_sky_set(rt_context* ctx, int k) {
+    SkySet& s = ctx->fr.skySet[k];
+    RT_TRY(dalloc_once(ctx, s.sky, (size_t)kSkySize * 16));
+    RT_TRY(dalloc_once(ctx, s.skyPdf, (size_t)kSkySize * 4));
+    RT_TRY(dalloc_once(ctx, s.skyCdf, (size_t)kSkySize * 4));
+    RT_TRY(dalloc_once(ctx, s.sun, (size_t)kSunSize * 16));
+    RT_TRY(dalloc_once(ctx, s.sunPdf, (size_t)kSunSize * 4));
+    RT_TRY(dalloc_once(ctx, s.sunCdf, (size_t)kSunSize * 4));
+    RT_TRY(dalloc_once(ctx, s.skyTree, (size_t)kSkyTreeNodes * 4));
+    RT_TRY(dalloc_once(ctx, s.sunTree, (size_t)kSunTreeNodes * 4));
+    RT_TRY(dalloc_once(ctx, s.lightSel, 16));
+    for (hipEvent_t* e : {&s.read, &s.specRead}) RT_TRY(rt_event(ctx, *e));
+    return RT_OK;
+}
+
+// The sky tables again, from the current parameters and environment (the environment setters)
+int rt_regenerate_sky(rt_context* ctx) {
+    ctx->fr.skyValid = false;
+    return update_sky(ctx);
+}
+
+// rt_time_stage(7): one sky-set generation into a spare set on the context stream; the current set and
+// its serial stay as they are.  The spare is the next set in turn, whose contents nothing reads once the
+// streams are idle (the caller's wait), or, on a context with one set, a set allocated here.
+int rt_time_sky_generation(rt_context* ctx) {
+    FrameResources& fr = ctx->fr;
+    const int spare = ctx->skySets > 1 ? (fr.skyCur + 1) % ctx->skySets : 1;
+    RT_TRY(alloc_sky_set(ctx, spare));
+    return generate_sky(ctx, fr.skySet[spare], ctx->stream);
+}
+
 int rt_frame_init(rt_context* ctx) {
     FrameResources& fr = ctx->fr;
     std::string err;
@@ -493,16 +563,19 @@ int rt_frame_init(rt_context* ctx) {
     RT_TRY(dalloc_once(ctx, fr.solar, 1800 * 4));
     RT_TRY(dalloc_once(ctx, fr.limb, 60 * 4));
     RT_TRY(dalloc_once(ctx, fr.cie, 30 * 4));
-    RT_TRY(dalloc_once(ctx, fr.sky, (size_t)kSkySize * 16));
-    RT_TRY(dalloc_once(ctx, fr.skyPdf, (size_t)kSkySize * 4));
-    RT_TRY(dalloc_once(ctx, fr.skyCdf, (size_t)kSkySize * 4));
-    RT_TRY(dalloc_once(ctx, fr.sun, (size_t)kSunSize * 16));
-    RT_TRY(dalloc_once(ctx, fr.sunPdf, (size_t)kSunSize * 4));
-    RT_TRY(dalloc_once(ctx, fr.sunCdf, (size_t)kSunSize * 4));
-    RT_TRY(dalloc_once(ctx, fr.scanSums, 512 * 4));
-    RT_TRY(dalloc_once(ctx, fr.skyTree, (size_t)kSkyTreeNodes * 4));
-    RT_TRY(dalloc_once(ctx, fr.sunTree, (size_t)kSunTreeNodes * 4));
-    RT_TRY(dalloc_once(ctx, fr.lightSel, 16));
+    {  // sky set 0, in the order a context without [scene] skySets has always allocated it
+        SkySet& k = fr.skySet[0];
+        RT_TRY(dalloc_once(ctx, k.sky, (size_t)kSkySize * 16));
+        RT_TRY(dalloc_once(ctx, k.skyPdf, (size_t)kSkySize * 4));
+        RT_TRY(dalloc_once(ctx, k.skyCdf, (size_t)kSkySize * 4));
+        RT_TRY(dalloc_once(ctx, k.sun, (size_t)kSunSize * 16));
+        RT_TRY(dalloc_once(ctx, k.sunPdf, (size_t)kSunSize * 4));
+        RT_TRY(dalloc_once(ctx, k.sunCdf, (size_t)kSunSize * 4));
+        RT_TRY(dalloc_once(ctx, fr.scanSums, 512 * 4));
+        RT_TRY(dalloc_once(ctx, k.skyTree, (size_t)kSkyTreeNodes * 4));
+        RT_TRY(dalloc_once(ctx, k.sunTree, (size_t)kSunTreeNodes * 4));
+        RT_TRY(dalloc_once(ctx, k.lightSel, 16));
+    }
     // texture sets ([scene] textureSets): the sets of one map are one allocation, set k k * kTexTexels in
     RT_TRY(dalloc_once(ctx, fr.texAlbedo, (size_t)ctx->texSets * kTexTexels * 8));
     RT_TRY(dalloc_once(ctx, fr.texNormal, (size_t)ctx->texSets * kTexTexels * 8));
@@ -601,6 +674,10 @@ int rt_frame_init(rt_context* ctx) {
             for (uint2* map : {fr.texAlbedo, fr.texNormal})
                 HIP_TRY(ctx, hipMemcpy(map + (size_t)k * kTexTexels, map, (size_t)kTexTexels * 8, hipMemcpyDeviceToDevice));
     }
+    // further sky sets ([scene] skySets), behind everything a context with one set allocates
+    for (int k = 1; k < ctx->skySets; ++k) RT_TRY(alloc_sky_set(ctx, k));
+    if (ctx->skySets > 1)
+        for (hipEvent_t* e : {&fr.skySet[0].read, &fr.skySet[0].specRead}) RT_TRY(rt_event(ctx, *e));
     HIP_TRY(ctx, hipMemset(fr.set[0].color, 0, P * 8));
     HIP_TRY(ctx, hipMemset(fr.set[0].normal, 0, P * 8));
     HIP_TRY(ctx, hipMemset(fr.set[0].albedo, 0, P * 8));
@@ -785,16 +862,17 @@ void fill_pt_params(const rt_context* ctx, int frame_num, int with_detail, const
     p.tlasNodes = bvh.tlasNodes;
     p.texAlbedo = fr.texAlbedo;
     p.texNormal = fr.texNormal;
-    p.skyBuffer = fr.sky;
-    p.sunBuffer = fr.sun;
-    p.skyCdf = fr.skyCdf;
-    p.sunCdf = fr.sunCdf;
-    p.skyTree = fr.skyTree;
-    p.sunTree = fr.sunTree;
-    p.lightSel = fr.lightSel;
+    const SkySet& sk = fr.sky();  // the current sky set, held by value from here on
+    p.skyBuffer = sk.sky;
+    p.sunBuffer = sk.sun;
+    p.skyCdf = sk.skyCdf;
+    p.sunCdf = sk.sunCdf;
+    p.skyTree = sk.skyTree;
+    p.sunTree = sk.sunTree;
+    p.lightSel = sk.lightSel;
     memcpy(p.sunDir, fr.sunDir, 12);
-    p.cosThetaMax = fr.cosThetaMax;
-    p.oneMinusCosThetaMax = 1.0f - fr.cosThetaMax;
+    p.cosThetaMax = sk.cosThetaMax;
+    p.oneMinusCosThetaMax = 1.0f - sk.cosThetaMax;
     sun_frame(fr.sunDir, p.sunT, p.sunB);
     p.colorOut = cam.color;
     p.normalOut = cam.normal;
@@ -847,8 +925,8 @@ bool spec_on(const rt_context* ctx) {
 
 // whether the camera and shade kernels launched with `a` wrote what ones launched with `b` would:
 // the same parameters but for those they do not read (or that only select the later kernels)
-bool spec_matches(const PathTraceParams& a, uint64_t epochA, uint64_t matA, const PathTraceParams& b, uint64_t epochB,
-                  uint64_t matB) {
+bool spec_matches(const PathTraceParams& a, uint64_t epochA, uint64_t matA, uint64_t skyA, const PathTraceParams& b,
+                  uint64_t epochB, uint64_t matB, uint64_t skyB) {
     // they read the LBVH set of the frame that launched them, the next frame reads the other: both
     // hold the same build (tests/test_gpu_bvh.py) exactly when no vertex update came between them
     if (epochA != epochB) return false;
@@ -857,6 +935,9 @@ bool spec_matches(const PathTraceParams& a, uint64_t epochA, uint64_t matA, cons
     // and the tables' buffers are recycled, so triMat's address does not tell its contents: the
     // table's serial does
     if (matA != matB) return false;
+    // the sky tables: a set's address does not tell its contents either, the sets being taken in turn
+    // (update_sky); every generation, into whichever set, moves the serial
+    if (skyA != skyB) return false;
     // emitter sampling: whether a launch samples a list at all selects its kernels and must agree
     if ((a.emHeader != nullptr) != (b.emHeader != nullptr)) return false;
     PathTraceParams x = a, y = b;
@@ -978,7 +1059,8 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
     if (fr.spec.valid) {
         fr.spec.valid = false;
         HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->specDone, 0));
-        reuse = !side && spec_matches(p, ctx->geomEpoch, ctx->matSerial, fr.spec.p, fr.spec.epoch, fr.spec.matSerial);
+        reuse = !side && spec_matches(p, ctx->geomEpoch, ctx->matSerial, fr.skySerial, fr.spec.p, fr.spec.epoch,
+                                        fr.spec.matSerial, fr.spec.skySerial);
         reuseShade = reuse && fr.spec.shade;
         if (!reuse) p.ws.countersZeroed = 0;  // their counts are in the block: the launcher clears it
         fr.specCounts = reuse ? 1 : 2;  // folded into the frame's (or cleared) ahead of the next ones
@@ -1038,6 +1120,12 @@ int rt_path_trace(rt_context* ctx, int frame_num, int with_detail) {
         rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
         HIP_TRY(ctx, hipEventRecord(tab.read, ctx->stream));
         tab.readValid = true;
+    }
+    // ... and the sky set, which the next generation into it waits for (update_sky)
+    if (ctx->skySets > 1) {
+        SkySet& sk = fr.sky();
+        HIP_TRY(ctx, hipEventRecord(sk.read, ctx->stream));
+        sk.readValid = true;
     }
     if (p.triDisp) ctx->lbvh().dispTraced = true;  // later path traces on this build see no motion of the geometry
     if (!ctx->postStream) {  // block b + 2 is zeroed by this frame's resolve, enqueued above
@@ -1330,6 +1418,11 @@ int launch_spec_camera(rt_context* ctx) {
         HIP_TRY(ctx, hipEventRecord(tab.specRead, ctx->sideStream));
         tab.specValid = true;
     }
+    if (ctx->skySets > 1) {  // the sky set these kernels read
+        SkySet& sk = fr.sky();
+        HIP_TRY(ctx, hipEventRecord(sk.specRead, ctx->sideStream));
+        sk.specValid = true;
+    }
     fr.syncZeroed[b] = false;
     fr.spec.valid = true;
     ++fr.specLaunched;
@@ -1337,6 +1430,7 @@ int launch_spec_camera(rt_context* ctx) {
     fr.spec.block = b;
     fr.spec.epoch = ctx->geomEpoch;  // of this frame's LBVH, built or checked by enqueue_frame just before
     fr.spec.matSerial = ctx->matSerial;
+    fr.spec.skySerial = fr.skySerial;
     fr.spec.p = p;
     return RT_OK;
 }
@@ -1612,8 +1706,8 @@ int rt_get_buffer(const rt_context* cctx, int name, void* dst, size_t bytes) {
         case RT_BUF_ALBEDO: src = fr.cur().albedo; break;
         case RT_BUF_DEPTH: src = fr.cur().depth; break;
         case RT_BUF_MOTION: src = fr.cur().motion; break;
-        case RT_BUF_SKY: src = fr.sky; break;
-        case RT_BUF_SUN: src = fr.sun; break;
+        case RT_BUF_SKY: src = fr.sky().sky; break;
+        case RT_BUF_SUN: src = fr.sky().sun; break;
         case RT_BUF_HISTOGRAM: src = fr.histogram; break;
         case RT_BUF_RGBA8:
             if (bytes < rt_buffer_bytes(ctx, name)) { ctx->err = "destination too small"; return RT_ERR_ARG; }

@@ -325,6 +325,9 @@ extern "C" hipError_t rtk_denoise_phase(DenoisePostParams* p, hipStream_t stream
 extern "C" hipError_t rtk_hdr_out(const uint2* color, float4* hdr, size_t n, hipStream_t stream);
 
 extern "C" hipError_t rtk_launch_sky(const SkyGenParams* p, hipStream_t stream);
+// ... under an environment: the sky table and pdf copied from envTable / envPdf instead of k_sky (sky.hip)
+extern "C" hipError_t rtk_launch_sky_env(const SkyGenParams* p, const float4* envTable, const float* envPdf,
+                                         hipStream_t stream);
 // MipmapGen (texture.hip): levels 1.. of a square 16-bit chain whose level 0 is in place
 extern "C" hipError_t rtk_launch_mipgen(uint16_t* chain, int size, int levels, int channels, hipStream_t stream);
 // level 0 of a 4-channel chain from device memory (rt_upload_texture_set_device): `texels` ushort4

@@ -213,10 +213,20 @@ __global__ void k_light_select(const float* skyCdf, const float* sunCdf, float c
     out[3] = kTwoPi * (1.0f - cosThetaMax);
 }
 
-extern "C" hipError_t rtk_launch_sky(const SkyGenParams* p, hipStream_t stream) {
-    hipLaunchKernelGGL(k_sky, dim3(kSkySize / 256), dim3(256), 0, stream, *p);
-    hipError_t e = rtk_launch_scan(p->skyPdf, p->skyCdf, p->scanSums, kSkySize, kSkyScanBlock, stream);
-    if (e != hipSuccess) return e;
+// One sky generation.  envTable / envPdf (both or neither): an environment is active
+// (rt_set_environment), and the sky table and its pdf are copies of the context's environment table
+// instead of k_sky's output; the sun tables, the scans, the probe trees and lightSel as ever.
+extern "C" hipError_t rtk_launch_sky_env(const SkyGenParams* p, const float4* envTable, const float* envPdf,
+                                         hipStream_t stream) {
+    hipError_t e;
+    if (envTable) {
+        if ((e = hipMemcpyAsync(p->skyBuffer, envTable, (size_t)kSkySize * 16, hipMemcpyDeviceToDevice, stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(p->skyPdf, envPdf, (size_t)kSkySize * 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess)
+            return e;
+    } else {
+        hipLaunchKernelGGL(k_sky, dim3(kSkySize / 256), dim3(256), 0, stream, *p);
+    }
+    if ((e = rtk_launch_scan(p->skyPdf, p->skyCdf, p->scanSums, kSkySize, kSkyScanBlock, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sun, dim3(kSunSize / 256), dim3(256), 0, stream, *p);
     if ((e = rtk_launch_scan(p->sunPdf, p->sunCdf, p->scanSums, kSunSize, kSunScanBlock, stream)) != hipSuccess)
         return e;
@@ -227,4 +237,8 @@ extern "C" hipError_t rtk_launch_sky(const SkyGenParams* p, hipStream_t stream) 
     hipLaunchKernelGGL(k_light_select, dim3(1), dim3(1), 0, stream, (const float*)p->skyCdf, (const float*)p->sunCdf,
                        p->cosThetaMax, p->lightSel);
     return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_sky(const SkyGenParams* p, hipStream_t stream) {
+    return rtk_launch_sky_env(p, nullptr, nullptr, stream);
 }

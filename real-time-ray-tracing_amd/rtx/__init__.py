@@ -121,6 +121,12 @@ class TextureUpload(C.Structure):
                 ("ready_event", C.c_void_p)]
 
 
+class Environment(C.Structure):
+    """rt_environment: one environment image (rt_set_environment / rt_set_environment_device)."""
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
+                ("layout", C.c_uint32), ("scale", C.c_float), ("ready_event", C.c_void_p)]
+
+
 class Material(C.Structure):
     """rt_material: one entry of the material table (rt_set_materials)."""
     _fields_ = [("type", C.c_int32), ("flags", C.c_uint32), ("color", C.c_float * 3), ("emission", C.c_float * 3),
@@ -141,6 +147,10 @@ MAT_FLAG_FLAT = 1  # RT_MAT_FLAG_FLAT
 TEXTURE_SETS_MAX = 16  # RT_TEXTURE_SETS_MAX
 TEX_FORMAT_U16, TEX_FORMAT_U8 = 0, 1  # RT_TEX_FORMAT_*
 TEX_SIZE = 1024  # the atlases are TEX_SIZE x TEX_SIZE, 4 channels
+SKY_SETS_MAX = 8  # RT_SKY_SETS_MAX
+ENV_FORMAT_F32X4, ENV_FORMAT_F16X4 = 0, 1  # RT_ENV_FORMAT_*
+ENV_LAYOUT_TABLE, ENV_LAYOUT_LATLONG = 0, 1  # RT_ENV_LAYOUT_*
+ENV_TABLE_W, ENV_TABLE_H = 512, 256  # the sky table an environment becomes (RT_BUF_SKY)
 
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
@@ -228,6 +238,12 @@ SIGNATURES = {
     "rt_set_material_textures": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rt_get_material_textures": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rt_reset_material_textures": (C.c_int, [C.c_void_p]),
+    "rt_get_sky_sets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rt_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
+    "rt_set_environment_device": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
+    "rt_reset_environment": (C.c_int, [C.c_void_p]),
+    "rt_get_environment": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_environment_table": (C.c_int, [C.POINTER(Environment), C.c_void_p, C.c_void_p]),
 }
 MAT_CLASS_GLOSSY, MAT_CLASS_MICROFACET = 1, 2  # RT_MAT_CLASS_*
 MAT_CLASS_ALL = MAT_CLASS_GLOSSY | MAT_CLASS_MICROFACET
@@ -273,7 +289,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
                  target_fps: float = 60.0, mesh_file: str | None = None, tuning: dict | None = None,
                  geometry_motion: bool | None = None, max_triangles: int | None = None,
                  max_vertices: int | None = None, texture_sets: int | None = None,
-                 emitter_sampling: bool | None = None, emitter_probability: float | None = None) -> str:
+                 emitter_sampling: bool | None = None, emitter_probability: float | None = None,
+                 sky_sets: int | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
@@ -286,7 +303,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
     `texture_sets`: [scene] textureSets, the texture sets the context holds (None: the key is not
     written, one set).
     `emitter_sampling` / `emitter_probability`: [render] emitterSampling / emitterProbability, the initial
-    state of rt_set_emitter_sampling (None: the keys are not written; off, 0.5)."""
+    state of rt_set_emitter_sampling (None: the keys are not written; off, 0.5).
+    `sky_sets`: [scene] skySets, the sky sets the context holds (None: the key is not written, one set)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -306,6 +324,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
             f.write("maxVertices = %s\n" % max_vertices)
         if texture_sets is not None:
             f.write("textureSets = %s\n" % texture_sets)
+        if sky_sets is not None:
+            f.write("skySets = %s\n" % sky_sets)
         f.write("\n[render]\nspp = %d\n" % spp)
         if geometry_motion is not None:
             f.write("geometryMotion = %s\n" % ("true" if geometry_motion else "false"))
@@ -634,6 +654,52 @@ class RayTracer:
         """Every id back to set 0: no binding."""
         self._check(self.lib.rt_reset_material_textures(self.h), "rt_reset_material_textures")
 
+    # ---- sky sets and environment maps (include/rtx_amd.h)
+    @property
+    def sky_sets(self) -> int:
+        """The sky sets the context holds ([scene] skySets; 1 without the key)."""
+        n = C.c_uint32()
+        self._check(self.lib.rt_get_sky_sets(self.h, C.byref(n)), "rt_get_sky_sets")
+        return n.value
+
+    @property
+    def environment_active(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.rt_get_environment(self.h, C.byref(on)), "rt_get_environment")
+        return bool(on.value)
+
+    def set_environment(self, image, layout: int, scale: float = 1.0):
+        """rt_set_environment: `image` is a (height, width, 4) float32 or float16 array, TABLE (512 x 256,
+        the renderer's equal-area table) or LATLONG (row 0 at the zenith).  A host-style setter: it waits
+        for the renderer's streams; the array is free on return."""
+        a, e = _environment(image, layout, scale)
+        self._check(self.lib.rt_set_environment(self.h, C.byref(e)), "rt_set_environment")
+
+    def set_environment_device(self, tensor_or_ptr, width: int, height: int, fmt: int, layout: int, scale: float = 1.0,
+                               ready_event: int | None = None):
+        """rt_set_environment_device: width x height x 4 channels of float32 (ENV_FORMAT_F32X4) or float16
+        (ENV_FORMAT_F16X4) in device memory, given as a device pointer or an object with data_ptr() (a
+        contiguous torch tensor, whose size is checked); stream-ordered, no host wait; needs sky_sets >= 2.
+        ready_event as in update_vertices_device."""
+        if fmt not in (ENV_FORMAT_F32X4, ENV_FORMAT_F16X4):
+            raise ValueError("set_environment_device: fmt must be ENV_FORMAT_F32X4 or ENV_FORMAT_F16X4")
+        for name, v in (("width", width), ("height", height), ("layout", layout)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("set_environment_device: %s must fit 32 bits" % name)
+        ptr = tensor_or_ptr
+        if hasattr(tensor_or_ptr, "data_ptr"):
+            t = tensor_or_ptr
+            want = int(width) * int(height) * (16 if fmt == ENV_FORMAT_F32X4 else 8)
+            if t.numel() * t.element_size() != want or not t.is_contiguous():
+                raise ValueError("set_environment_device: the tensor must be contiguous and hold %d bytes" % want)
+            ptr = t.data_ptr()
+        e = Environment(int(ptr) if ptr else None, int(width), int(height), int(fmt), int(layout), float(scale), ready_event)
+        self._check(self.lib.rt_set_environment_device(self.h, C.byref(e)), "rt_set_environment_device")
+
+    def reset_environment(self):
+        """Back to the Hosek sky table (a host-style setter)."""
+        self._check(self.lib.rt_reset_environment(self.h), "rt_reset_environment")
+
     def trace_primary(self, frame_num: int = 1, detail: bool = False):
         self._check(self.lib.rt_trace_primary(self.h, frame_num, 1 if detail else 0), "rt_trace_primary")
 
@@ -856,6 +922,32 @@ def emitter_select(cdf, r: float):
     if rc != RT_OK:
         raise RtError("rt_emitter_select: %s" % ERRORS.get(rc, rc))
     return slot.value, np.float32(prob.value)
+
+
+def _environment(image, layout: int, scale: float):
+    """(array kept alive, Environment) of a (height, width, 4) float32 / float16 host image."""
+    a = np.asarray(image)
+    if a.dtype not in (np.float32, np.float16):
+        raise ValueError("environment: the image must be float32 or float16")
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("environment: the image must have the shape (height, width, 4)")
+    if not 0 <= int(layout) <= 0xFFFFFFFF:
+        raise ValueError("environment: layout must fit 32 bits")
+    a = np.ascontiguousarray(a)
+    fmt = ENV_FORMAT_F32X4 if a.dtype == np.float32 else ENV_FORMAT_F16X4
+    return a, Environment(a.ctypes.data, a.shape[1], a.shape[0], fmt, int(layout), float(scale), None)
+
+
+def environment_table(image, layout: int, scale: float = 1.0):
+    """rt_environment_table: (table (256, 512, 4) float32, pdf (256, 512) float32) that `image` gives as an
+    environment, the rule the device matches bit for bit.  Host only: no context, no device."""
+    a, e = _environment(image, layout, scale)
+    table = np.empty((ENV_TABLE_H, ENV_TABLE_W, 4), np.float32)
+    pdf = np.empty((ENV_TABLE_H, ENV_TABLE_W), np.float32)
+    rc = load_library().rt_environment_table(C.byref(e), table.ctypes.data, pdf.ctypes.data)
+    if rc != RT_OK:
+        raise RtError("rt_environment_table: %s" % ERRORS.get(rc, rc))
+    return table, pdf
 
 
 def default_material(id: int) -> Material:
