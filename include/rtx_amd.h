@@ -525,6 +525,82 @@ int rt_set_mesh_device(rt_context* ctx, const rt_mesh* device_mesh);
 int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32_t vertex_count,
                       uint32_t* adj_offsets, uint32_t* adj_corners, uint32_t* corner_slots);
 
+/* Skinned meshes (no reference counterpart): linear-blend skinning on the device.  A skin is a bind
+ * pose with up to RT_SKIN_INFLUENCES joints and weights per vertex; a pose is one 3 x 4 matrix per
+ * joint (12 floats, row-major, translation in column 3: 48 bytes per joint and frame where
+ * rt_update_vertices moves 12 bytes per vertex).  A rigid object is one joint with weight 1.
+ *
+ * The rule, in plain fp32 with one rounding per operation and nothing fused, for vertex v with rest
+ * position p, joints j[0..3], weights w[0..3], and each output row r = 0, 1, 2:
+ *     acc = +0
+ *     for k = 0, 1, 2, 3 in this order:
+ *         if w[k] == 0: continue                       (the joint's matrix is not read)
+ *         t   = ((M[j[k]][r][0] * px + M[j[k]][r][1] * py) + M[j[k]][r][2] * pz) + M[j[k]][r][3]
+ *         acc = acc + w[k] * t
+ *     out[r] = acc
+ * Weights are used as given: they are not normalised and need not sum to 1.  The skip is part of the
+ * rule: a NaN matrix in a joint that no non-zero weight names reaches no vertex.  The identity pose
+ * returns the rest position, except that a -0 component becomes +0.  rt_skin_vertices is the rule
+ * compiled for the host (no context, no device); the kernel compiles the same text and gives its bits.
+ *
+ * rt_set_skin / rt_reset_skin are host-style setters like rt_set_materials: they wait for the
+ * renderer's streams, drop what a synchronous draw traced ahead, and rt_set_skin copies the three
+ * arrays into device buffers of the context (the caller's arrays are free on return).  The first set
+ * allocates, by the vertex capacity ([scene] maxVertices): 48 bytes per vertex (rest 12, joints 8,
+ * weights 16, skinned positions 12) and RT_SKIN_JOINTS_MAX * 48 bytes of matrix staging.  Setting a
+ * skin moves no vertex and does not advance the geometry epoch.  A skin covers the whole mesh.
+ * Checked in this order, and on an error nothing changes: RT_ERR_ARG for a NULL ctx or struct;
+ * RT_ERR_ARG for a NULL array, vertex_count == 0 or joint_count outside 1..RT_SKIN_JOINTS_MAX;
+ * RT_ERR_STATE before rt_init; RT_ERR_ARG for vertex_count != rt_get_info().vertexCount; RT_ERR_ARG
+ * for a joint index >= joint_count (slots of weight 0 included) or a weight that is negative or not
+ * finite; RT_ERR_HIP for a failed allocation or copy (a failed copy leaves the context without a skin
+ * rather than with a mixed one).  Never RT_ERR_DEVICE.
+ *
+ * rt_pose_skin_device belongs to the family of rt_update_vertices_device: the host is never
+ * synchronised and no stream is drained.  The skinning kernel runs on the update stream (the side
+ * stream of a pipelined context, else the context stream) behind ready_event — or, with NULL, behind
+ * everything enqueued on the context stream so far — and behind the builds and the update a vertex
+ * update waits for; the whole-mesh vertex update follows it on the same stream, fed the rule's
+ * positions.  From there on everything is as after rt_update_vertices_device(all vertices): normals,
+ * epoch + 1, geometry motion, the context stream following the read of `matrices`, frames in flight
+ * keeping their geometry, a draw's work ahead built and traced again.  `matrices` is caller-owned
+ * device memory, 16-byte aligned, unchanged until read.  Matrices are not inspected: non-finite
+ * results behave as non-finite positions given to rt_update_vertices_device do.
+ * RT_ERR_ARG for a NULL ctx or struct, NULL or misaligned matrices; RT_ERR_STATE before rt_init or
+ * without a skin; RT_ERR_ARG for joint_count != the skin's; RT_ERR_HIP for a failed launch.  Never
+ * RT_ERR_DEVICE.
+ * rt_pose_skin: host matrices, copied synchronously into the staging buffer once the previous update
+ * has ended (rt_update_vertices' staging rule), then the device path; ready_event is ignored.
+ *
+ * Interactions: rt_set_mesh* drops the skin, which belonged to the old vertices: a pose is
+ * RT_ERR_STATE until a new rt_set_skin.  rt_update_vertices* with a skin set simply override
+ * positions until the next pose, which starts from the rest pose again.  Every rank of a multi-GPU
+ * run calls with the same data.  A context that never calls rt_set_skin allocates and launches
+ * exactly what it did without the feature. */
+#define RT_SKIN_INFLUENCES 4
+#define RT_SKIN_JOINTS_MAX 4096
+typedef struct rt_skin {
+    const float*    rest_xyz;     /* vertex_count xyz triples: the bind pose */
+    const uint16_t* joints;       /* vertex_count x 4 */
+    const float*    weights;      /* vertex_count x 4 */
+    uint32_t vertex_count;        /* == rt_get_info().vertexCount: a skin covers the whole mesh */
+    uint32_t joint_count;         /* 1 .. RT_SKIN_JOINTS_MAX */
+} rt_skin;
+typedef struct rt_pose {
+    const float* matrices;        /* joint_count x 12 floats, row-major 3 x 4 */
+    uint32_t joint_count;         /* == the skin's */
+    void* ready_event;            /* device variant: hipEvent_t or NULL, as in rt_update_vertices_device */
+} rt_pose;
+int rt_set_skin(rt_context* ctx, const rt_skin* host);
+int rt_reset_skin(rt_context* ctx);
+int rt_get_skin(const rt_context* ctx, uint32_t* vertex_count, uint32_t* joint_count); /* 0, 0 without a skin */
+int rt_pose_skin(rt_context* ctx, const rt_pose* host);
+int rt_pose_skin_device(rt_context* ctx, const rt_pose* dev);
+/* The rule on the host: xyz_out receives vertex_count xyz triples; `matrices` holds joint_count
+ * matrices.  RT_ERR_ARG, with xyz_out untouched: a NULL pointer, vertex_count == 0, joint_count outside
+ * 1..RT_SKIN_JOINTS_MAX, a joint index >= joint_count, a weight that is negative or not finite. */
+int rt_skin_vertices(const rt_skin* host, const float* matrices, float* xyz_out);
+
 /* Geometry motion vectors (no reference counterpart): off by default, and off nothing changes.  On,
  * the RT_BUF_MOTION G-buffer of a frame accounts for the vertices' displacement between the LBVH
  * build the frame is traced on and the build before it: a pixel whose sample 0 hit a triangle at
@@ -840,7 +916,10 @@ int rt_sync(rt_context* ctx);
  * current positions from a copy: arrays and epoch stay as they are, 6 = a whole-mesh set (rt_set_mesh_device)
  * fed the current mesh from a copy, arrays and epoch likewise left as they are, 7 = one sky-set
  * generation into a spare set, under the environment when one is active, the current set and its serial
- * left as they are) and returns the total milliseconds between the first launch and the end of the last. */
+ * left as they are, 8 = one whole-mesh pose of the skin (RT_ERR_STATE without one): the skinning kernel
+ * under the matrices of the last rt_pose_skin (identity if there was none since rt_set_skin) and the
+ * whole-mesh vertex update behind it, which like stage 5 is fed the current positions from a copy, so
+ * arrays and epoch stay as they are) and returns the total milliseconds between the first launch and the end of the last. */
 int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms);
 
 /* Stage 6 split by HIP events between its launches: `iters` whole-mesh sets one after the other,

@@ -20,6 +20,7 @@
 #include "gaussian_tables.h"
 #include "mat_kernels.h"
 #include "rtmath.h"
+#include "skin_kernels.h"
 #include "toml_lite.h"
 
 namespace {
@@ -879,9 +880,10 @@ struct MeshChange {
     const uint32_t* indices;  // device memory, [triCount * 3]
     uint32_t triCount, nverts;
 };
-static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t first, uint32_t count, hipEvent_t ready,
-                                 bool srcReady, bool bump, const MeshChange* mesh = nullptr) {
-    hipStream_t u = ctx->postStream ? ctx->sideStream : ctx->stream;
+static hipStream_t update_stream(const rt_context* ctx) { return ctx->postStream ? ctx->sideStream : ctx->stream; }
+
+// what an update on U waits for: its source, and the builds and the update still using what it writes
+static int order_vertex_update(rt_context* ctx, hipStream_t u, hipEvent_t ready, bool srcReady) {
     if (!srcReady) {
         if (ready) {
             HIP_TRY(ctx, hipStreamWaitEvent(u, ready, 0));
@@ -896,6 +898,16 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
         for (const BvhBufs& b : ctx->bvh)
             if (b.sideBuilt) HIP_TRY(ctx, hipStreamWaitEvent(u, b.buildDone, 0));
     if (ctx->geomDoneValid && ctx->geomStream != u) HIP_TRY(ctx, hipStreamWaitEvent(u, ctx->geomDone, 0));
+    return RT_OK;
+}
+
+// `ordered`: the caller has made U wait already (order_vertex_update) and enqueued the source's producer
+// on it (a pose's skinning kernel)
+static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t first, uint32_t count, hipEvent_t ready,
+                                 bool srcReady, bool bump, const MeshChange* mesh = nullptr, bool ordered = false) {
+    hipStream_t u = update_stream(ctx);
+    if (!ordered)
+        if (int rc = order_vertex_update(ctx, u, ready, srcReady)) return rc;
     hipEvent_t* marks = ctx->meshMarks;  // rt_time_mesh_set only
     if (mesh) {
         MeshSetParams m;
@@ -931,6 +943,7 @@ static int enqueue_vertex_update(rt_context* ctx, const float* src, uint32_t fir
             ctx->matDevice = false;
             ++ctx->matSerial;
             ctx->prevVertsValid = false;  // geometry motion: the next build is a first build
+            ctx->skinSet = false;         // a skin belongs to the vertices it was set for (rt_set_skin)
         }
     }
     GeomUpdateParams p;
@@ -1042,6 +1055,104 @@ int rt_set_mesh(rt_context* ctx, const rt_mesh* mesh) {
     HIP_TRY(ctx, hipMemcpy(ctx->dIdxStage, mesh->indices, ni * 4, hipMemcpyHostToDevice));
     const MeshChange mc{ctx->dIdxStage, mesh->triangle_count, mesh->vertex_count};
     return enqueue_vertex_update(ctx, ctx->dVertStage, 0, mesh->vertex_count, nullptr, true, true, &mc);
+}
+
+// ---------------------------------------------------------------- skinned meshes
+//
+// Check order of rt_set_skin: NULL ctx / skin, the arguments that need no context state, the init state,
+// the vertex count, the arrays' contents.
+int rt_set_skin(rt_context* ctx, const rt_skin* skin) {
+    if (!ctx || !skin) return RT_ERR_ARG;
+    if (const char* bad = skin_shape_fault(skin)) { ctx->err = std::string("rt_set_skin: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_set_skin before rt_init"; return RT_ERR_STATE; }
+    if (skin->vertex_count != ctx->nv) {
+        ctx->err = "rt_set_skin: vertex_count " + std::to_string(skin->vertex_count) + " is not the mesh's " +
+                   std::to_string(ctx->nv) + ": a skin covers the whole mesh";
+        return RT_ERR_ARG;
+    }
+    uint32_t at = 0;
+    if (const char* bad = skin_content_fault(skin, at)) {
+        ctx->err = "rt_set_skin: vertex " + std::to_string(at) + ": " + bad;
+        return RT_ERR_ARG;
+    }
+    // a pose in flight reads the arrays; camera rays traced ahead are dropped as by every setter
+    if (int rc = sync_streams(ctx, false)) return rc;
+    RT_TRY(dalloc_once(ctx, ctx->dSkinRest, (size_t)ctx->capNV * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dSkinJoints, (size_t)ctx->capNV * 8));
+    RT_TRY(dalloc_once(ctx, ctx->dSkinWeights, (size_t)ctx->capNV * 16));
+    RT_TRY(dalloc_once(ctx, ctx->dSkinned, (size_t)ctx->capNV * 12));
+    RT_TRY(dalloc_once(ctx, ctx->dSkinMats, (size_t)kSkinJointsMax * kSkinMatrixFloats * 4));
+    const size_t nv = skin->vertex_count;
+    std::vector<float> ident((size_t)skin->joint_count * kSkinMatrixFloats, 0.0f);
+    for (uint32_t j = 0; j < skin->joint_count; ++j)
+        ident[(size_t)j * 12] = ident[(size_t)j * 12 + 5] = ident[(size_t)j * 12 + 10] = 1.0f;
+    ctx->skinSet = false;  // a failed copy leaves no skin rather than a mixed one
+    HIP_TRY(ctx, hipMemcpy(ctx->dSkinRest, skin->rest_xyz, nv * 12, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dSkinJoints, skin->joints, nv * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dSkinWeights, skin->weights, nv * 16, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dSkinMats, ident.data(), ident.size() * 4, hipMemcpyHostToDevice));
+    ctx->skinSet = true;
+    ctx->skinJoints = skin->joint_count;
+    return RT_OK;
+}
+
+int rt_reset_skin(rt_context* ctx) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_reset_skin before rt_init"; return RT_ERR_STATE; }
+    if (int rc = sync_streams(ctx, false)) return rc;
+    ctx->skinSet = false;  // the buffers stay allocated for the next set
+    return RT_OK;
+}
+
+int rt_get_skin(const rt_context* ctx, uint32_t* vertex_count, uint32_t* joint_count) {
+    if (!ctx || !vertex_count || !joint_count) return RT_ERR_ARG;
+    *vertex_count = ctx->skinSet ? ctx->nv : 0u;
+    *joint_count = ctx->skinSet ? ctx->skinJoints : 0u;
+    return RT_OK;
+}
+
+// One pose on the update stream: the skinning kernel behind what a vertex update waits for, then the
+// whole-mesh update reading its output (`src` null), or for rt_time_stage(8) the given copy of the
+// current positions.
+static int enqueue_pose(rt_context* ctx, const float* matrices, hipEvent_t ready, bool srcReady, bool bump,
+                        const float* src = nullptr) {
+    hipStream_t u = update_stream(ctx);
+    if (int rc = order_vertex_update(ctx, u, ready, srcReady)) return rc;
+    SkinParams p;
+    p.rest = ctx->dSkinRest;
+    p.joints = ctx->dSkinJoints;
+    p.weights = ctx->dSkinWeights;
+    p.matrices = matrices;
+    p.out = ctx->dSkinned;
+    p.nverts = ctx->nv;
+    HIP_TRY(ctx, rtk_launch_skin(&p, u));
+    return enqueue_vertex_update(ctx, src ? src : ctx->dSkinned, 0, ctx->nv, nullptr, true, bump, nullptr, true);
+}
+
+static int check_pose(rt_context* ctx, const rt_pose* pose, bool device, const char* who) {
+    if (!ctx || !pose) return RT_ERR_ARG;
+    if (!pose->matrices) { ctx->err = std::string(who) + ": matrices must not be NULL"; return RT_ERR_ARG; }
+    if (device && ((uintptr_t)pose->matrices & 15u) != 0) { ctx->err = std::string(who) + ": matrices must be 16-byte aligned"; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = std::string(who) + " before rt_init"; return RT_ERR_STATE; }
+    if (!ctx->skinSet) { ctx->err = std::string(who) + " without a skin (rt_set_skin; rt_set_mesh drops it)"; return RT_ERR_STATE; }
+    if (pose->joint_count != ctx->skinJoints) {
+        ctx->err = std::string(who) + ": joint_count " + std::to_string(pose->joint_count) + " is not the skin's " +
+                   std::to_string(ctx->skinJoints);
+        return RT_ERR_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_pose_skin_device(rt_context* ctx, const rt_pose* pose) {
+    if (int rc = check_pose(ctx, pose, true, "rt_pose_skin_device")) return rc;
+    return enqueue_pose(ctx, pose->matrices, (hipEvent_t)pose->ready_event, false, true);
+}
+
+int rt_pose_skin(rt_context* ctx, const rt_pose* pose) {
+    if (int rc = check_pose(ctx, pose, false, "rt_pose_skin")) return rc;
+    if (int rc = vertex_stage(ctx)) return rc;  // the matrix staging, once no earlier pose reads it
+    HIP_TRY(ctx, hipMemcpy(ctx->dSkinMats, pose->matrices, (size_t)pose->joint_count * kSkinMatrixFloats * 4, hipMemcpyHostToDevice));
+    return enqueue_pose(ctx, ctx->dSkinMats, nullptr, true, true);
 }
 
 // ---------------------------------------------------------------- geometry motion vectors
@@ -1570,7 +1681,8 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
         return rc != RT_OK ? rc : rc2;
     }
     const MeshChange same{ctx->dIdxStage, ctx->mesh.triCount, ctx->nv};  // stage 6
-    if (stage == 5 || stage == 6) {  // the current positions (and indices) again, from a copy: the arrays and the epoch stay as they are
+    if (stage == 8 && !ctx->skinSet) { ctx->err = "rt_time_stage(8) without a skin (rt_set_skin)"; return RT_ERR_STATE; }
+    if (stage == 5 || stage == 6 || stage == 8) {  // the current positions (and indices) again, from a copy: the arrays and the epoch stay as they are
         int rc = sync_streams(ctx, false);
         if (rc == RT_OK) rc = vertex_stage(ctx);
         if (rc != RT_OK) return rc;
@@ -1592,6 +1704,7 @@ int rt_time_stage(rt_context* ctx, int stage, int iters, float* total_ms) {
         else if (stage == 7) rc = rt_time_sky_generation(ctx);
         else if (stage == 5) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false);
         else if (stage == 6) rc = enqueue_vertex_update(ctx, ctx->dVertStage, 0, ctx->nv, nullptr, true, false, &same);
+        else if (stage == 8) rc = enqueue_pose(ctx, ctx->dSkinMats, nullptr, true, false, ctx->dVertStage);
         else if (stage == 1) rc = rt_trace_primary(ctx, 1 + i, 0);
         else if (stage == 2) rc = rt_path_trace(ctx, 1 + i, 0);
         else if (stage == 3) {

@@ -375,6 +375,17 @@ struct rt_context {
     uint64_t prevVertsEpoch = 0;
     bool built = false;                 // an LBVH has been built, at geometry epoch builtEpoch (the last build's)
     uint64_t builtEpoch = 0;
+    // skinned meshes (rt_set_skin / rt_pose_skin*): null until the first rt_set_skin, and
+    // then nothing here is allocated or launched.  A pose runs k_skin_vertices (skin.hip) on the update
+    // stream into dSkinned and feeds that to the whole-mesh vertex update, so dSkinned has the ordering of
+    // an update's source and dVerts' (geomDone); the skin's arrays are written behind a wait for every stream.
+    bool skinSet = false;               // a skin is set (rt_set_mesh* drops it)
+    uint32_t skinJoints = 0;            // its joint count; its vertex count is nv
+    float* dSkinRest = nullptr;         // [capNV * 3] the bind pose
+    uint16_t* dSkinJoints = nullptr;    // [capNV * 4]
+    float* dSkinWeights = nullptr;      // [capNV * 4]
+    float* dSkinned = nullptr;          // [capNV * 3] the last pose's positions
+    float* dSkinMats = nullptr;         // [RT_SKIN_JOINTS_MAX * 12] rt_pose_skin's matrices (identity after rt_set_skin)
     // per-triangle materials (rt_set_triangle_materials): null until the first set and after a reset,
     // and then every launch is the one of a context without the feature.  The pool below keeps the
     // allocation across resets; the host copy gives the census of ids (triMatCount) and from it the
@@ -545,6 +556,8 @@ extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits 
 extern "C" int ensure_emitter_lists(rt_context* ctx);  // context.cpp: the existing LBVH sets' emitter-list buffers
 inline bool emitter_active(const rt_context* ctx) { return ctx->emitterOn && ctx->matCustom && ctx->matEmits; }
 extern "C" int ensure_geometry_motion(rt_context* ctx);  // context.cpp: dPrevVerts and the existing LBVH sets' triDisp
+const char* skin_shape_fault(const rt_skin* s);  // skin.cpp: what is wrong with a skin's pointers or counts, or null
+const char* skin_content_fault(const rt_skin* s, uint32_t& vertex);  // ... or with its joints and weights, and at which vertex
 std::string rt_data_dir();
 void rt_camera_update(const rt_camera& in, int renderW, int renderH, HostCamera& c);
 void rt_input_control_update(rt_context* ctx, float deltaTime);  // input.cpp

@@ -109,6 +109,17 @@ class Mesh(C.Structure):
                 ("triangle_count", C.c_uint32), ("ready_event", C.c_void_p)]
 
 
+class Skin(C.Structure):
+    """rt_skin: a bind pose with four joints and weights per vertex (rt_set_skin, rt_skin_vertices)."""
+    _fields_ = [("rest_xyz", C.c_void_p), ("joints", C.c_void_p), ("weights", C.c_void_p),
+                ("vertex_count", C.c_uint32), ("joint_count", C.c_uint32)]
+
+
+class Pose(C.Structure):
+    """rt_pose: one 3 x 4 matrix per joint (rt_pose_skin / rt_pose_skin_device)."""
+    _fields_ = [("matrices", C.c_void_p), ("joint_count", C.c_uint32), ("ready_event", C.c_void_p)]
+
+
 class MaterialUpdate(C.Structure):
     """rt_material_update: one device material set (rt_set_triangle_materials_device)."""
     _fields_ = [("ids", C.c_void_p), ("first", C.c_uint32), ("count", C.c_uint32), ("classes", C.c_uint32),
@@ -217,6 +228,12 @@ SIGNATURES = {
     "rt_set_mesh_device": (C.c_int, [C.c_void_p, C.POINTER(Mesh)]),
     "rt_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_time_mesh_set": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "rt_set_skin": (C.c_int, [C.c_void_p, C.POINTER(Skin)]),
+    "rt_reset_skin": (C.c_int, [C.c_void_p]),
+    "rt_get_skin": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rt_pose_skin": (C.c_int, [C.c_void_p, C.POINTER(Pose)]),
+    "rt_pose_skin_device": (C.c_int, [C.c_void_p, C.POINTER(Pose)]),
+    "rt_skin_vertices": (C.c_int, [C.POINTER(Skin), C.c_void_p, C.c_void_p]),
     "rt_set_geometry_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_get_geometry_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_set_emitter_sampling": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
@@ -250,6 +267,7 @@ MAT_CLASS_ALL = MAT_CLASS_GLOSSY | MAT_CLASS_MICROFACET
 IMAGE_PPM_RGBA8, IMAGE_PFM_HDR = 0, 1
 DRAW_ASYNC = 1  # rt_draw_device flag
 BUF_SET1, BUF_SET2, BUF_SET3 = 0x100, 0x200, 0x300  # rt_bind_buffer: further G-buffer sets (frame pipelining)
+SKIN_INFLUENCES, SKIN_JOINTS_MAX = 4, 4096  # RT_SKIN_*
 GBUFFER_SETS = 4  # G-buffer sets a pipelined context cycles through (rt_set_post_stream; RT_GBUFFER_SETS)
 
 _lib = None
@@ -499,6 +517,48 @@ class RayTracer:
             raise ValueError("set_mesh_device: nv and ntri must fit 32 bits")
         m = Mesh(xyz_ptr, int(nv), idx_ptr, int(ntri), ready_event)
         self._check(self.lib.rt_set_mesh_device(self.h, C.byref(m)), "rt_set_mesh_device")
+
+    # ---- skinned meshes (rt_set_skin / rt_pose_skin*, include/rtx_amd.h)
+    def set_skin(self, rest: np.ndarray, joints: np.ndarray, weights: np.ndarray, joint_count: int):
+        """The mesh's skin from host arrays: (nv, 3) float32 rest positions, (nv, 4) uint16 joint indices and
+        (nv, 4) float32 weights, C-contiguous, nv the mesh's vertex count.  A host-style setter: it waits
+        for the renderer's streams; the arrays are free on return.  No vertex moves until a pose."""
+        s = _skin(rest, joints, weights, joint_count, "set_skin")
+        self._check(self.lib.rt_set_skin(self.h, C.byref(s)), "rt_set_skin")
+
+    def reset_skin(self):
+        """No skin: a pose is an error until the next set_skin (a host-style setter)."""
+        self._check(self.lib.rt_reset_skin(self.h), "rt_reset_skin")
+
+    @property
+    def skin(self):
+        """(vertex_count, joint_count) of the skin, (0, 0) without one."""
+        nv, nj = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.rt_get_skin(self.h, C.byref(nv), C.byref(nj)), "rt_get_skin")
+        return nv.value, nj.value
+
+    def pose_skin(self, matrices: np.ndarray):
+        """One pose from host matrices, a C-contiguous (J, 3, 4) or (J, 12) float32 array, J the skin's
+        joint count: every vertex moves to the skinning rule's position, and the normals and every later
+        build_bvh / draw follow as after a whole-mesh update_vertices."""
+        m = _pose_matrices(matrices, "pose_skin")
+        p = Pose(m.ctypes.data, len(m), None)
+        self._check(self.lib.rt_pose_skin(self.h, C.byref(p)), "rt_pose_skin")
+
+    def pose_skin_device(self, tensor_or_ptr, joint_count: int, ready_event: int | None = None):
+        """The same from device memory (joint_count x 12 float32, 16-byte aligned), given as a device pointer
+        or an object with data_ptr() (a contiguous float32 torch tensor, whose size is checked);
+        asynchronous, no host wait.  ready_event as in update_vertices_device."""
+        if not 0 <= int(joint_count) <= 0xFFFFFFFF:
+            raise ValueError("pose_skin_device: joint_count must fit 32 bits")
+        ptr = tensor_or_ptr
+        if hasattr(tensor_or_ptr, "data_ptr"):
+            t = tensor_or_ptr
+            if t.element_size() != 4 or not t.is_floating_point() or t.numel() != int(joint_count) * 12 or not t.is_contiguous():
+                raise ValueError("pose_skin_device: the tensor must be contiguous float32 and hold joint_count x 12 values")
+            ptr = t.data_ptr()
+        p = Pose(int(ptr) if ptr else None, int(joint_count), ready_event)
+        self._check(self.lib.rt_pose_skin_device(self.h, C.byref(p)), "rt_pose_skin_device")
 
     def time_mesh_set(self, iters: int = 1):
         """(ingest, adjacency, normals) milliseconds summed over `iters` whole-mesh sets of the
@@ -936,6 +996,45 @@ def _environment(image, layout: int, scale: float):
     a = np.ascontiguousarray(a)
     fmt = ENV_FORMAT_F32X4 if a.dtype == np.float32 else ENV_FORMAT_F16X4
     return a, Environment(a.ctypes.data, a.shape[1], a.shape[0], fmt, int(layout), float(scale), None)
+
+
+def _skin(rest, joints, weights, joint_count, who):
+    """The rt_skin of three host arrays, which it refuses unless they are what the library reads."""
+    for a, dt, cols, name in ((rest, np.float32, 3, "rest"), (joints, np.uint16, 4, "joints"), (weights, np.float32, 4, "weights")):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != 2 or a.shape[1] != cols:
+            raise ValueError("%s: %s must be an (n, %d) %s array" % (who, name, cols, np.dtype(dt).name))
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s: %s must be C-contiguous" % (who, name))
+    if not len(rest) == len(joints) == len(weights) or len(rest) > 0xFFFFFFFF:
+        raise ValueError("%s: rest, joints and weights must have one row per vertex" % who)
+    if not 0 <= int(joint_count) <= 0xFFFFFFFF:
+        raise ValueError("%s: joint_count must fit 32 bits" % who)
+    return Skin(rest.ctypes.data, joints.ctypes.data, weights.ctypes.data, len(rest), int(joint_count))
+
+
+def _pose_matrices(matrices, who):
+    """A pose's host matrices as a (J, 12) view, refused unless C-contiguous float32 (J, 3, 4) or (J, 12)."""
+    m = matrices
+    if not isinstance(m, np.ndarray) or m.dtype != np.float32 or not (
+            (m.ndim == 3 and m.shape[1:] == (3, 4)) or (m.ndim == 2 and m.shape[1] == 12)):
+        raise ValueError("%s: matrices must be a (J, 3, 4) or (J, 12) float32 array" % who)
+    if not m.flags["C_CONTIGUOUS"]:
+        raise ValueError("%s: matrices must be C-contiguous" % who)
+    if len(m) > 0xFFFFFFFF:
+        raise ValueError("%s: the joint count must fit 32 bits" % who)
+    return m.reshape(len(m), 12)
+
+
+def skin_vertices(rest, joints, weights, matrices) -> np.ndarray:
+    """rt_skin_vertices: the skinning rule on the host (no context, no device), the positions a pose of
+    `matrices` gives the skin, bit for bit what the device computes.  The joint count is len(matrices)."""
+    m = _pose_matrices(matrices, "skin_vertices")
+    s = _skin(rest, joints, weights, len(m), "skin_vertices")
+    out = np.zeros((len(rest), 3), np.float32)
+    rc = load_library().rt_skin_vertices(C.byref(s), m.ctypes.data, out.ctypes.data)
+    if rc != RT_OK:
+        raise RtError("rt_skin_vertices: %s" % ERRORS.get(rc, rc))
+    return out
 
 
 def environment_table(image, layout: int, scale: float = 1.0):

@@ -59,17 +59,29 @@ class FramePipeline:
         self.need = ([gbuffer_rows(info.renderHeight, world, r) for r in range(world)]
                      if self.denoise is not None else None)
 
-    def frame(self, f: int, hdr: bool = False, vertices=None, vertices_ready=None):
+    def frame(self, f: int, hdr: bool = False, vertices=None, vertices_ready=None, pose=None, pose_ready=None):
         """LBVH rebuild, path trace, (gather,) denoise + post of frame f, enqueued asynchronously.
 
         vertices: a device float32 tensor (n, 3), the positions of vertices [0, n) from this frame
         on (rt_update_vertices_device), applied ahead of the rebuild.  vertices_ready: a recorded
         torch.cuda.Event the read of the tensor waits for, when the host animates on a stream of
         its own; None: the read follows everything enqueued on the renderer's stream so far.  The
-        tensor must stay unchanged until then; every rank passes the same data."""
+        tensor must stay unchanged until then; every rank passes the same data.
+
+        pose: a device float32 tensor (J, 3, 4) or (J, 12), one matrix per joint of the context's skin
+        (rt_pose_skin_device), applied where vertices is; pose_ready as vertices_ready.  One of the
+        two per frame."""
         import torch
 
         rt = self.rt
+        if pose is not None:
+            if vertices is not None:
+                raise ValueError("pose and vertices both move the whole frame's geometry: pass one of them")
+            if (pose.dtype != torch.float32 or not pose.is_contiguous() or not pose.is_cuda
+                    or not ((pose.dim() == 3 and tuple(pose.shape[1:]) == (3, 4)) or (pose.dim() == 2 and pose.shape[1] == 12))):
+                raise ValueError("pose must be a contiguous (J, 3, 4) or (J, 12) float32 device tensor")
+            ev = None if pose_ready is None else pose_ready.cuda_event
+            rt.pose_skin_device(pose, pose.shape[0], ev)
         if vertices is not None:
             if (vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3
                     or not vertices.is_contiguous() or not vertices.is_cuda):
