@@ -24,6 +24,6 @@ float bluenoise(const uint8_t* tables, int px, int py, int sampleIdx, int dim);
 F2 concentric_disk(F2 u);
 void generate_ray(const Camera& c, int ix, int iy, F2 pix, F2 ap, F3& orig, F3& dir, F3& centerDir, F2& sampleUv);
 float ray_cone_width(const Camera& c, int ix, int iy);
-void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out);
+void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out, float* hitUV = nullptr);
 
 }  // namespace orc

@@ -68,6 +68,11 @@ typedef struct OrcHit {
 // RaySceneIntersect core (traverse.cuh:64-225 without the material bookkeeping) for n rays.
 // rays: [n][6] orig xyz, dir xyz.  threads: host threads to use (0 = all).
 void orc_intersect(const OrcScene* scene, const float* rays, uint32_t n, OrcHit* hits, int threads);
+// ... and into hitUV [n][2] the barycentrics of the closest hit itself: (u, v) as they stood when
+// objectIdx was set (0, 0 on a miss).  OrcHit.u / .v are HitInfo's, which TraverseBvh overwrites at
+// every triangle test that passes, also one that only ties the closest t; the reference shades with
+// these (fakeNormal is built from them).  A call of its own, so that OrcHit keeps its size.
+void orc_intersect_uv(const OrcScene* scene, const float* rays, uint32_t n, OrcHit* hits, float* hitUV, int threads);
 
 typedef struct OrcCamera {
     float pos[3];

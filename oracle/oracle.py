@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
         L.orc_smooth_normals.restype = None
         L.orc_intersect.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
         L.orc_intersect.restype = None
+        L.orc_intersect_uv.argtypes = [C.POINTER(Scene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
+        L.orc_intersect_uv.restype = None
         L.orc_primary_rays.argtypes = [C.POINTER(CameraIn), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
         L.orc_primary_rays.restype = None
@@ -172,6 +174,20 @@ def intersect(bvh: dict, rays: np.ndarray, threads: int = 0) -> np.ndarray:
                bvh["triangles"].shape[0], bvh["batch_count"])
     lib().orc_intersect(C.byref(sc), rays.ctypes.data, n, hits.ctypes.data, threads)
     return hits
+
+
+def intersect_uv(bvh: dict, rays: np.ndarray, threads: int = 0):
+    """intersect, and the (u, v) of the closest hit itself as an (n, 2) float32 array: the pair the
+    reference shades with.  The hits' own u / v are HitInfo's, which every triangle test that passes
+    overwrites, also one that only ties the closest t."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    n = rays.shape[0]
+    hits = np.zeros(n, HIT_DTYPE)
+    uv = np.zeros((n, 2), np.float32)
+    sc = Scene(bvh["triangles"].ctypes.data, bvh["nodes"].ctypes.data, bvh["tlas_nodes"].ctypes.data,
+               bvh["triangles"].shape[0], bvh["batch_count"])
+    lib().orc_intersect_uv(C.byref(sc), rays.ctypes.data, n, hits.ctypes.data, uv.ctypes.data, threads)
+    return hits, uv
 
 
 def default_camera(width: int, height: int) -> CameraIn:

@@ -134,14 +134,14 @@ static bool watertight(F3 org, F3 dir, const float* tri, float tCur, float& t, f
 
 struct StackEntry { uint32_t idx, blasOffset, isBlas, isLeaf; float t; };
 
-void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out) {
+void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out, float* hitUV) {
     const Node* nodes = (const Node*)sc->nodes;
     const Node* tlas = (const Node*)sc->tlasNodes;
     F3 inv = f3(safe_divide(1.0f, dir.x), safe_divide(1.0f, dir.y), safe_divide(1.0f, dir.z));
     float t = kRayMax;
     int objectIdx = -1;
     F3 nrm = f3(0.0f), pos = f3(kRayMax), fake = f3(0.0f);
-    float u = 0.0f, v = 0.0f;
+    float u = 0.0f, v = 0.0f, hitU = 0.0f, hitV = 0.0f;
     float errorP = 1e-7f, errorT = 1e-7f, offset = 1e-7f;
     uint32_t visits = 0, tests = 0, dropped = 0, iters = 0, maxDepth = 0;
 
@@ -175,6 +175,7 @@ void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out) {
                 if (tt < t) {
                     t = tt;
                     objectIdx = (int)li;
+                    hitU = u; hitV = v;
                     F3 v1 = f3(tri[0], tri[1], tri[2]), v2 = f3(tri[3], tri[4], tri[5]), v3 = f3(tri[6], tri[7], tri[8]);
                     nrm = normalize(cross(v2 - v1, v3 - v1));
                     float w = -dot(nrm, v1);
@@ -235,19 +236,21 @@ void intersect_one(const OrcScene* sc, F3 org, F3 dir, OrcHit& out) {
     out.ndr = ndr;
     out.nodeVisits = visits; out.triTests = tests; out.droppedPushes = dropped; out.iterations = iters;
     out.maxDepth = maxDepth;
+    if (hitUV) { hitUV[0] = hitU; hitUV[1] = hitV; }
 }
 
 }  // namespace orc
 
 using namespace orc;
 
-extern "C" void orc_intersect(const OrcScene* scene, const float* rays, uint32_t n, OrcHit* hits, int threads) {
+extern "C" void orc_intersect_uv(const OrcScene* scene, const float* rays, uint32_t n, OrcHit* hits, float* hitUV,
+                                 int threads) {
     if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
     if (threads < 1) threads = 1;
     auto work = [&](uint32_t lo, uint32_t hi) {
         for (uint32_t r = lo; r < hi; ++r) {
             const float* ry = rays + (size_t)r * 6;
-            intersect_one(scene, f3(ry[0], ry[1], ry[2]), f3(ry[3], ry[4], ry[5]), hits[r]);
+            intersect_one(scene, f3(ry[0], ry[1], ry[2]), f3(ry[3], ry[4], ry[5]), hits[r], hitUV ? hitUV + (size_t)r * 2 : nullptr);
         }
     };
     if (threads == 1 || n < 1024) { work(0, n); return; }
@@ -263,4 +266,8 @@ extern "C" void orc_intersect(const OrcScene* scene, const float* rays, uint32_t
             }
         });
     for (auto& th : pool) th.join();
+}
+
+extern "C" void orc_intersect(const OrcScene* scene, const float* rays, uint32_t n, OrcHit* hits, int threads) {
+    orc_intersect_uv(scene, rays, n, hits, nullptr, threads);
 }
