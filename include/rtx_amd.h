@@ -1098,6 +1098,61 @@ typedef struct rt_ray_query {
     void* done_event;   /* hipEvent_t or NULL: recorded on the context stream behind the kernel */
 } rt_ray_query;
 int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q);
+
+/* Surface queries (no reference counterpart): a device ray query that also answers what its hits hit,
+ * for collision response (the normal), semantic sensors (the material id), secondary rays (the
+ * re-projected hit point and the reference's ray offset) and Doppler / optical-flow sensors (how the
+ * hit point moved since the last build).  The tracer of rt_trace_rays_device runs on q->rays and
+ * writes the same records to rays.hits; behind it on the context stream a dense pass writes one
+ * surface record per ray, RT_SURFACE_FLOATS(flags) floats, as 16-byte quads:
+ *
+ *   quad  .x .y .z                                                     .w
+ *   0     pos: the hit point re-projected onto the triangle            offset: the reference's ray offset
+ *         (miss: RayMax x 3)                                            (errorT + errorP; miss: 1e-7f)
+ *   1     normal: geometric, facing the ray (miss: 0, -1, 0)           normalDotRayDir after the flip (miss: -0.0f)
+ *   2     fakeNormal: the interpolated vertex normal, flipped to       uint32 bits: 0..15 the material id the path
+ *         the geometric one's side (miss: 0, -1, 0)                    tracer reads for the triangle, 16 front face
+ *                                                                      (isRayIntoSurface), 17 hit; a miss: 0
+ *   3     RT_SURFACE_MOTION only: the hit point's displacement since   0
+ *         the build before, d3 (1 - u - v) + d1 u + d2 v of the
+ *         corners' (rt_set_geometry_motion; zeros when the build
+ *         recorded none, or geometry motion is off, and on a miss)
+ *
+ * The rule is RaySceneIntersect's tail (traverse.cuh:192-217) on the record's (t, triangle, u, v): the
+ * renderer's finalize_hit, the function its path tracer shades with, so the values are the reference's
+ * bit for bit (errorT = gamma(16) |t|, as RayTriangleWatertight leaves it).  The material id is
+ * materialsIdx[triangle] as the path tracer reads it at the call: [render] materialOverride if set, the
+ * table of rt_set_triangle_materials(_device) current at the call, 3 without one.  A secondary ray
+ * starts at pos + offset * normal (pos - offset * normal to go through the surface), not at
+ * org + t * dir, which hits the triangle it left.  A record whose triangle index is not one of the
+ * traced build's, -1 included, is finished as a miss and reads nothing.  Not provided: tmin / tmax (as
+ * for the ray query), UV coordinates or other vertex attributes, a host-buffer variant.
+ *
+ * RT_SURFACE_FROM_HITS: no traversal; rays.hits is read, the records of an earlier query on the same
+ * rays and the same build (the caller's responsibility: the pass reads the build current at this call).
+ *
+ * Ordering: everything rt_trace_rays_device documents.  The host is never synchronised, no stream is
+ * drained, what a synchronous draw traced ahead is kept, the path tracer's workspace, RT_ARR_PT_QUEUE,
+ * rt_get_ray_count and the pending geometry motion of the next frame are left as they were.
+ * rays.ready_event is waited for ahead of the tracer, rays.done_event is recorded behind the surface
+ * pass, and the LBVH set and the material table are held until that pass has read them: a later build
+ * or rt_set_triangle_materials_device waits on the device.  n == 0 is RT_OK and enqueues nothing but
+ * done_event.
+ *
+ * RT_ERR_ARG: NULL ctx or q (checked first); then, before the init state: every argument error of
+ * rt_trace_rays_device on q->rays, unknown bits in flags, with n > 0 a NULL or not 16-byte aligned
+ * surface, and with RT_SURFACE_FROM_HITS a rays.iters that is not NULL or RT_QUERY_ANY_HIT in
+ * rays.flags.  RT_ERR_STATE before rt_init; RT_ERR_HIP for a failed launch.  It never returns
+ * RT_ERR_DEVICE. */
+#define RT_SURFACE_FROM_HITS 1u  /* rays.hits is input: no traversal, only the surface pass */
+#define RT_SURFACE_MOTION    2u  /* four quads per ray instead of three */
+#define RT_SURFACE_FLOATS(flags) (((flags) & RT_SURFACE_MOTION) ? 16u : 12u)
+typedef struct rt_surface_query {
+    rt_ray_query rays;   /* as rt_trace_rays_device; rays.flags may hold RT_QUERY_ANY_HIT */
+    float* surface;      /* device, 16-B aligned, n x RT_SURFACE_FLOATS(flags) floats */
+    uint32_t flags;
+} rt_surface_query;
+int rt_trace_surfaces_device(rt_context* ctx, const rt_surface_query* q);
 size_t rt_array_bytes(const rt_context* ctx, int what);
 
 #ifdef __cplusplus

@@ -1864,47 +1864,121 @@ int rt_trace_rays(rt_context* ctx, const float* rays, uint32_t n, float* hits, u
 // drains nothing, keeps what a synchronous draw traced ahead, and uses none of the path tracer's
 // workspace (the counter blocks, the queues, hitRec*, pathL, syncZeroed) nor the ray counter.
 // Check order: NULL ctx / q, then the other argument checks, then the init state.
+
+// what is wrong with a query's arguments, or null (rt_trace_rays_device, rt_trace_surfaces_device)
+static const char* ray_query_fault(const rt_ray_query* q) {
+    if (q->org_stride < 3u || q->dir_stride < 3u) return "strides are in floats and at least 3";
+    if (q->n > RT_QUERY_MAX_RAYS) return "more rays than RT_QUERY_MAX_RAYS";
+    if ((q->flags & ~RT_QUERY_ANY_HIT) != 0u) return "unknown flags";
+    if (q->n > 0u && (!q->org || !q->dir || !q->hits)) return "org, dir and hits must not be NULL";
+    if (((uintptr_t)q->hits & 15u) != 0) return "hits must be 16-byte aligned";
+    if ((((uintptr_t)q->org | (uintptr_t)q->dir | (uintptr_t)q->iters) & 3u) != 0) return "org, dir and iters must be 4-byte aligned";
+    return nullptr;
+}
+
+// the tracer of a query with n > 0 on LBVH set b, enqueued on s
+static int enqueue_ray_trace(rt_context* ctx, const rt_ray_query* q, const BvhBufs& b, hipStream_t s) {
+    RayQueryParams p;
+    p.nodes = b.nodes;
+    p.tlasNodes = b.tlasNodes;
+    p.triPos = b.triPos;
+    p.org = q->org;
+    p.dir = q->dir;
+    p.orgStride = q->org_stride;
+    p.dirStride = q->dir_stride;
+    p.n = q->n;
+    p.hits = reinterpret_cast<float4*>(q->hits);
+    p.iters = q->iters;
+    p.fetch = ctx->queryFetch;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->queryFetch, 0, 512, s));
+    // the queue tracers' grid policy (rt_frame_init: cus x tracePerCu, [tuning] tracePerCu)
+    HIP_TRY(ctx, rtk_launch_trace_rays(&p, ctx->fr.ws.traceBlocks, (q->flags & RT_QUERY_ANY_HIT) != 0u, s));
+    return RT_OK;
+}
+
+// The set a query read is held against the builds that would overwrite it, from this point of s on: a
+// pipelined context's next build but one (rt_build_bvh waits for readDone), a synchronous draw's
+// prebuild (prebuild_next_bvh)
+static int hold_query_set(rt_context* ctx, BvhBufs& b, hipStream_t s) {
+    if (ctx->postStream) {
+        HIP_TRY(ctx, hipEventRecord(b.readDone, s));
+        b.readInFlight = true;
+    } else {
+        HIP_TRY(ctx, hipEventRecord(b.queryDone, s));
+        b.queryInFlight = true;
+    }
+    return RT_OK;
+}
+
 int rt_trace_rays_device(rt_context* ctx, const rt_ray_query* q) {
     if (!ctx || !q) return RT_ERR_ARG;
-    const char* bad = nullptr;
-    if (q->org_stride < 3u || q->dir_stride < 3u) bad = "strides are in floats and at least 3";
-    else if (q->n > RT_QUERY_MAX_RAYS) bad = "more rays than RT_QUERY_MAX_RAYS";
-    else if ((q->flags & ~RT_QUERY_ANY_HIT) != 0u) bad = "unknown flags";
-    else if (q->n > 0u && (!q->org || !q->dir || !q->hits)) bad = "org, dir and hits must not be NULL";
-    else if (((uintptr_t)q->hits & 15u) != 0) bad = "hits must be 16-byte aligned";
-    else if ((((uintptr_t)q->org | (uintptr_t)q->dir | (uintptr_t)q->iters) & 3u) != 0) bad = "org, dir and iters must be 4-byte aligned";
-    if (bad) { ctx->err = std::string("rt_trace_rays_device: ") + bad; return RT_ERR_ARG; }
+    if (const char* bad = ray_query_fault(q)) { ctx->err = std::string("rt_trace_rays_device: ") + bad; return RT_ERR_ARG; }
     if (!ctx->inited) { ctx->err = "rt_trace_rays_device before rt_init"; return RT_ERR_STATE; }
     hipStream_t s = ctx->stream;
     if (q->n > 0u) {
         if (q->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)q->ready_event, 0));
         if (int rc = wait_bvh(ctx)) return rc;  // the current set's build, wherever it ran
-        RayQueryParams p;
         BvhBufs& b = ctx->lbvh();
+        if (int rc = enqueue_ray_trace(ctx, q, b, s)) return rc;
+        if (int rc = hold_query_set(ctx, b, s)) return rc;
+    }
+    if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));
+    return RT_OK;
+}
+
+// Surface queries (surface_rays.hip): rt_trace_rays_device's tracer, or none (RT_SURFACE_FROM_HITS),
+// and behind it on the context stream the dense surface pass over the records.  Everything the ray
+// query leaves alone this leaves alone; dispTraced is not touched either, since a query never
+// consumes the displacement a frame is still to apply.  Check order: NULL ctx / q, the ray query's
+// argument checks, the surface query's own, then the init state.
+int rt_trace_surfaces_device(rt_context* ctx, const rt_surface_query* q) {
+    if (!ctx || !q) return RT_ERR_ARG;
+    const rt_ray_query* r = &q->rays;
+    const bool fromHits = (q->flags & RT_SURFACE_FROM_HITS) != 0u;
+    const char* bad = ray_query_fault(r);
+    if (!bad) {
+        if ((q->flags & ~(RT_SURFACE_FROM_HITS | RT_SURFACE_MOTION)) != 0u) bad = "unknown surface flags";
+        else if (r->n > 0u && !q->surface) bad = "surface must not be NULL";
+        else if (r->n > 0u && ((uintptr_t)q->surface & 15u) != 0) bad = "surface must be 16-byte aligned";
+        else if (fromHits && r->iters) bad = "RT_SURFACE_FROM_HITS traces nothing: iters must be NULL";
+        else if (fromHits && (r->flags & RT_QUERY_ANY_HIT)) bad = "RT_SURFACE_FROM_HITS traces nothing: RT_QUERY_ANY_HIT must be clear";
+    }
+    if (bad) { ctx->err = std::string("rt_trace_surfaces_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_trace_surfaces_device before rt_init"; return RT_ERR_STATE; }
+    hipStream_t s = ctx->stream;
+    if (r->n > 0u) {
+        if (r->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)r->ready_event, 0));
+        if (int rc = wait_bvh(ctx)) return rc;
+        BvhBufs& b = ctx->lbvh();
+        if (!fromHits)
+            if (int rc = enqueue_ray_trace(ctx, r, b, s)) return rc;
+        RaySurfaceParams p;
         p.nodes = b.nodes;
         p.tlasNodes = b.tlasNodes;
         p.triPos = b.triPos;
-        p.org = q->org;
-        p.dir = q->dir;
-        p.orgStride = q->org_stride;
-        p.dirStride = q->dir_stride;
-        p.n = q->n;
-        p.hits = reinterpret_cast<float4*>(q->hits);
-        p.iters = q->iters;
-        p.fetch = ctx->queryFetch;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->queryFetch, 0, 512, s));
-        // the queue tracers' grid policy (rt_frame_init: cus x tracePerCu, [tuning] tracePerCu)
-        HIP_TRY(ctx, rtk_launch_trace_rays(&p, ctx->fr.ws.traceBlocks, (q->flags & RT_QUERY_ANY_HIT) != 0u, s));
-        // the set is held against the builds that would overwrite it: a pipelined context's next build
-        // but one (rt_build_bvh waits for readDone), a synchronous draw's prebuild (prebuild_next_bvh)
-        if (ctx->postStream) {
-            HIP_TRY(ctx, hipEventRecord(b.readDone, s));
-            b.readInFlight = true;
-        } else {
-            HIP_TRY(ctx, hipEventRecord(b.queryDone, s));
-            b.queryInFlight = true;
+        p.triNrm = b.triNrm;
+        // the displacement the set's build recorded, whether or not a path trace has applied it
+        p.triDisp = b.dispValid ? b.triDisp : nullptr;
+        // the material table of a path trace enqueued now (fill_pt_params): the override wins over it
+        p.materialOverride = ctx->materialOverride;
+        p.triMat = ctx->materialOverride >= 0 ? nullptr : ctx->dTriMat;
+        p.triCount = b.triCount;
+        p.triCountPadded = b.triCountPadded;
+        p.org = r->org;
+        p.dir = r->dir;
+        p.orgStride = r->org_stride;
+        p.dirStride = r->dir_stride;
+        p.n = r->n;
+        p.hits = reinterpret_cast<const float4*>(r->hits);
+        p.surface = reinterpret_cast<float4*>(q->surface);
+        HIP_TRY(ctx, rtk_launch_ray_surface(&p, (q->flags & RT_SURFACE_MOTION) != 0u, s));
+        if (int rc = hold_query_set(ctx, b, s)) return rc;  // behind the surface kernel: triDisp is the set's
+        if (p.triMat && ctx->matPoolReady) {  // a later rt_set_triangle_materials_device writes behind this reader
+            rt_context::MatTable& tab = ctx->matPool[ctx->matCur];
+            HIP_TRY(ctx, hipEventRecord(tab.read, s));
+            tab.readValid = true;
         }
     }
-    if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));
+    if (r->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)r->done_event, s));
     return RT_OK;
 }

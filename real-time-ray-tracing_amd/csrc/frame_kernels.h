@@ -389,3 +389,24 @@ struct RayQueryParams {
 };
 // grid: min(maxBlocks, ceil(n / 256)) workgroups
 extern "C" hipError_t rtk_launch_trace_rays(const RayQueryParams* p, uint32_t maxBlocks, int anyHit, hipStream_t stream);
+
+// The surface pass of a device ray query (surface_rays.hip, rt_trace_surfaces_device): the rays and
+// their hit records in, finalize_hit's surface record out, three float4 per ray (four with motion)
+struct RaySurfaceParams {
+    const void* nodes;       // the LBVH set, as RayQueryParams
+    const void* tlasNodes;
+    const float4* triPos;
+    const float4* triNrm;    // [triCountPadded][3]
+    const float4* triDisp;   // [triCountPadded][3] or null: the motion quad is zero
+    const uint8_t* triMat;   // [triCountPadded] or null: 3 everywhere (update_material)
+    int materialOverride;    // >= 0: that id for every triangle
+    uint32_t triCount, triCountPadded;  // of the set's build; a record's index outside [0, triCountPadded) is a miss
+    const float* org;
+    const float* dir;
+    uint32_t orgStride, dirStride;
+    uint32_t n;              // 1 .. RT_QUERY_MAX_RAYS
+    const float4* hits;      // [n] the records of rtk_launch_trace_rays
+    float4* surface;         // [n][3], or [n][4] with motion
+};
+// grid: ceil(n / 256) workgroups, one thread per ray; motion: the four-quad record
+extern "C" hipError_t rtk_launch_ray_surface(const RaySurfaceParams* p, int motion, hipStream_t stream);

@@ -103,6 +103,11 @@ class RayQuery(C.Structure):
                 ("ready_event", C.c_void_p), ("done_event", C.c_void_p)]
 
 
+class SurfaceQuery(C.Structure):
+    """rt_surface_query: one device surface query (rt_trace_surfaces_device)."""
+    _fields_ = [("rays", RayQuery), ("surface", C.c_void_p), ("flags", C.c_uint32)]
+
+
 class Mesh(C.Structure):
     """rt_mesh: an indexed mesh for rt_set_mesh / rt_set_mesh_device."""
     _fields_ = [("xyz", C.c_void_p), ("vertex_count", C.c_uint32), ("indices", C.c_void_p),
@@ -165,6 +170,13 @@ ENV_TABLE_W, ENV_TABLE_H = 512, 256  # the sky table an environment becomes (RT_
 
 QUERY_ANY_HIT = 1          # RT_QUERY_ANY_HIT
 QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
+SURFACE_FROM_HITS, SURFACE_MOTION = 1, 2  # RT_SURFACE_*
+
+
+def surface_floats(flags: int) -> int:
+    """RT_SURFACE_FLOATS: floats per ray of a surface record."""
+    return 16 if flags & SURFACE_MOTION else 12
+
 
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(StripExchange))
 HOOK_HISTOGRAM, HOOK_ROWS, HOOK_GBUFFERS = 0, 1, 2
@@ -210,6 +222,7 @@ SIGNATURES = {
     "rt_time_frame_kernels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayQuery)]),
+    "rt_trace_surfaces_device": (C.c_int, [C.c_void_p, C.POINTER(SurfaceQuery)]),
     "rt_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rt_array_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "rt_save_camera": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -939,6 +952,24 @@ class RayTracer:
         q = RayQuery(org_ptr, int(org_stride), dir_ptr, int(dir_stride), int(n), hits_ptr, iters_ptr,
                      QUERY_ANY_HIT if any_hit else 0, ready_event, done_event)
         self._check(self.lib.rt_trace_rays_device(self.h, C.byref(q)), "rt_trace_rays_device")
+
+    def trace_surfaces_device(self, org_ptr: int, dir_ptr: int, n: int, hits_ptr: int, surface_ptr: int, *,
+                              org_stride: int = 3, dir_stride: int = 3, iters_ptr: int | None = None,
+                              any_hit: bool = False, from_hits: bool = False, motion: bool = False,
+                              ready_event: int | None = None, done_event: int | None = None):
+        """rt_trace_surfaces_device: trace_rays_device's query, and behind it the surface pass that writes
+        n records of 12 float32 (16 with motion) at surface_ptr: position and ray offset, geometric normal
+        and its dot with the direction, shading normal and the material / front-face / hit word, and with
+        motion the hit point's displacement.  from_hits: nothing is traced, the records at hits_ptr (an
+        earlier query of the same rays on the same build) are read.  rtx.query.trace(surface=True) and
+        rtx.query.surfaces are the torch-tensor forms."""
+        for name, v in (("n", n), ("org_stride", org_stride), ("dir_stride", dir_stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("trace_surfaces_device: %s must fit 32 bits" % name)
+        rays = RayQuery(org_ptr, int(org_stride), dir_ptr, int(dir_stride), int(n), hits_ptr, iters_ptr,
+                        QUERY_ANY_HIT if any_hit else 0, ready_event, done_event)
+        q = SurfaceQuery(rays, surface_ptr, (SURFACE_FROM_HITS if from_hits else 0) | (SURFACE_MOTION if motion else 0))
+        self._check(self.lib.rt_trace_surfaces_device(self.h, C.byref(q)), "rt_trace_surfaces_device")
 
     def get_buffer(self, name: str, shape=None, dtype=np.uint8) -> np.ndarray:
         if shape is None:

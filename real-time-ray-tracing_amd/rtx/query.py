@@ -1,9 +1,16 @@
-"""Device ray queries on torch tensors (rt_trace_rays_device, include/rtx_amd.h).
+"""Device ray queries on torch tensors (rt_trace_rays_device, rt_trace_surfaces_device, include/rtx_amd.h).
 
 ``trace(rt, origins, directions)`` traces n rays that live in device tensors against the BVH of the
 last ``build_bvh`` / draw and returns their hit records as a device tensor, without a host
 synchronisation and without a copy of the inputs: visibility, line of sight, picking, collision and
 ray-cast sensors against geometry the host animates on the device (``update_vertices_device``).
+
+``trace(..., surface=True)`` also returns what the hits hit, one surface record per ray: the
+re-projected hit point and the reference's ray offset, the geometric and the shading normal, the
+material id, front face and hit flags, and with ``motion=True`` the hit point's displacement since the
+build before (views: ``position`` .. ``is_hit``).  ``surfaces(rt, origins, directions, hits)`` computes
+the same records from the hit records of an earlier query, without a traversal.  ``spawn_origins``
+gives the origins of secondary rays, so that query -> surfaces -> second query runs on the device.
 
 The query runs on the renderer's stream (``set_stream``).  ``trace`` may be called from any torch
 stream: it hands the renderer an event recorded on ``torch.cuda.current_stream()`` to wait for, and
@@ -30,7 +37,38 @@ def _rays(name, x, torch):
     return n, int(stride)
 
 
-def trace(rt, origins, directions, *, any_hit: bool = False, want_iters: bool = False, out=None):
+def _dense(name, x, shape, torch):
+    """An optional result tensor, or the hit records `surfaces` reads: contiguous float32 of this shape."""
+    if x is not None and (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != shape
+                          or not x.is_contiguous()):
+        raise ValueError("%s must be a contiguous (n, %d) float32 tensor" % (name, shape[1]))
+
+
+def _check(rt, origins, directions, dense, torch):
+    """The host-checkable refusals of a query, then the device checks; returns (n, strides, device).
+    dense: (name, tensor or None, columns) of the (n, columns) tensors beside the rays."""
+    n, org_stride = _rays("origins", origins, torch)
+    nd, dir_stride = _rays("directions", directions, torch)
+    if nd != n:
+        raise ValueError("origins and directions must hold the same number of rays (%d, %d)" % (n, nd))
+    if n > (1 << 30):
+        raise ValueError("at most 2^30 rays per query")
+    for name, x, cols in dense:
+        _dense(name, x, (n, cols), torch)
+    for name, x in (("origins", origins), ("directions", directions)):  # the device checks come last
+        if not x.is_cuda:
+            raise ValueError("%s must be on the renderer's device, not on %s" % (name, x.device))
+    if directions.device != origins.device or any(x is not None and x.device != origins.device for _, x, _ in dense):
+        raise ValueError("origins, directions%s must be on one device" % "".join(", " + name for name, _, _ in dense))
+    dev = origins.device
+    dev_id = rt.info().deviceId
+    if dev_id >= 0 and dev.index is not None and dev.index != dev_id:
+        raise ValueError("the rays are on %s, the renderer on device %d" % (dev, dev_id))
+    return n, org_stride, dir_stride, dev
+
+
+def trace(rt, origins, directions, *, any_hit: bool = False, want_iters: bool = False, out=None,
+          surface: bool = False, motion: bool = False, surface_out=None):
     """Hit records of the rays (origins[i, :3], directions[i, :3]).
 
     origins, directions: float32 device tensors of shape (n, 3..8) with a unit inner stride; the row
@@ -38,41 +76,64 @@ def trace(rt, origins, directions, *, any_hit: bool = False, want_iters: bool = 
     ``rays[:, 4:7]`` of one interleaved (n, 8) tensor) is passed on, nothing is copied.  Directions
     need not be normalised.  any_hit: each ray stops at the first hit the traversal records (same
     hit / miss answer, t >= the closest t).  out: an (n, 4) contiguous float32 tensor for the records.
+    surface: also the surface records (rt_trace_surfaces_device), an (n, 12) float32 tensor, (n, 16)
+    with motion (which needs surface); surface_out: a contiguous tensor of that shape for them.
 
     Returns hits (n, 4) float32: t (1e11 on a miss), the triangle index as int32 bits (-1), u, v (see
-    ``split``), and with want_iters also the traversal iterations per ray as an (n,) int32 tensor."""
+    ``split``); with surface (hits, surf); with want_iters also the traversal iterations per ray as an
+    (n,) int32 tensor, last."""
     import torch
 
-    n, org_stride = _rays("origins", origins, torch)
-    nd, dir_stride = _rays("directions", directions, torch)
-    if nd != n:
-        raise ValueError("origins and directions must hold the same number of rays (%d, %d)" % (n, nd))
-    if n > (1 << 30):
-        raise ValueError("at most 2^30 rays per query")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32
-                            or tuple(out.shape) != (n, 4) or not out.is_contiguous()):
-        raise ValueError("out must be a contiguous (n, 4) float32 tensor")
-    for name, x in (("origins", origins), ("directions", directions)):  # the device checks come last
-        if not x.is_cuda:
-            raise ValueError("%s must be on the renderer's device, not on %s" % (name, x.device))
-    if directions.device != origins.device or (out is not None and out.device != origins.device):
-        raise ValueError("origins, directions and out must be on one device")
-    dev = origins.device
-    dev_id = rt.info().deviceId
-    if dev_id >= 0 and dev.index is not None and dev.index != dev_id:
-        raise ValueError("the rays are on %s, the renderer on device %d" % (dev, dev_id))
+    if (motion or surface_out is not None) and not surface:
+        raise ValueError("motion and surface_out belong to surface=True")
+    cols = 16 if motion else 12
+    dense = (("out", out, 4),) + ((("surface_out", surface_out, cols),) if surface else ())
+    n, org_stride, dir_stride, dev = _check(rt, origins, directions, dense, torch)
     cur = torch.cuda.current_stream(dev)
     with torch.cuda.device(dev):
         hits = out if out is not None else torch.empty((n, 4), dtype=torch.float32, device=dev)
         iters = torch.empty(n, dtype=torch.int32, device=dev) if want_iters else None
+        surf = None
+        if surface:
+            surf = surface_out if surface_out is not None else torch.empty((n, cols), dtype=torch.float32, device=dev)
         ready, done = torch.cuda.Event(), torch.cuda.Event()
         ready.record(cur)
         done.record(cur)  # creates the handle; the renderer records it again behind the kernel
-        rt.trace_rays_device(origins.data_ptr(), directions.data_ptr(), n, hits.data_ptr(), org_stride=org_stride,
-                             dir_stride=dir_stride, iters_ptr=iters.data_ptr() if want_iters else None,
-                             any_hit=any_hit, ready_event=ready.cuda_event, done_event=done.cuda_event)
+        kw = dict(org_stride=org_stride, dir_stride=dir_stride, iters_ptr=iters.data_ptr() if want_iters else None,
+                  any_hit=any_hit, ready_event=ready.cuda_event, done_event=done.cuda_event)
+        if surface:
+            rt.trace_surfaces_device(origins.data_ptr(), directions.data_ptr(), n, hits.data_ptr(), surf.data_ptr(),
+                                     motion=motion, **kw)
+        else:
+            rt.trace_rays_device(origins.data_ptr(), directions.data_ptr(), n, hits.data_ptr(), **kw)
         cur.wait_event(done)
-    return (hits, iters) if want_iters else hits
+    res = (hits,) + ((surf,) if surface else ()) + ((iters,) if want_iters else ())
+    return res if len(res) > 1 else hits
+
+
+def surfaces(rt, origins, directions, hits, *, motion: bool = False, out=None):
+    """Surface records of rays whose hit records exist (RT_SURFACE_FROM_HITS): no traversal.
+
+    hits: the contiguous (n, 4) float32 records of an earlier query of the same rays on the build that is
+    current now (that it is the same build is the caller's responsibility); the rays as in ``trace``.
+    out: a contiguous (n, 12) float32 tensor, (n, 16) with motion.  Returns the records."""
+    import torch
+
+    cols = 16 if motion else 12
+    if hits is None:
+        raise ValueError("hits must be a contiguous (n, 4) float32 tensor")
+    n, org_stride, dir_stride, dev = _check(rt, origins, directions, (("hits", hits, 4), ("out", out, cols)), torch)
+    cur = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        surf = out if out is not None else torch.empty((n, cols), dtype=torch.float32, device=dev)
+        ready, done = torch.cuda.Event(), torch.cuda.Event()
+        ready.record(cur)
+        done.record(cur)  # creates the handle; the renderer records it again behind the kernel
+        rt.trace_surfaces_device(origins.data_ptr(), directions.data_ptr(), n, hits.data_ptr(), surf.data_ptr(),
+                                 org_stride=org_stride, dir_stride=dir_stride, from_hits=True, motion=motion,
+                                 ready_event=ready.cuda_event, done_event=done.cuda_event)
+        cur.wait_event(done)
+    return surf
 
 
 def split(hits):
@@ -96,3 +157,69 @@ def u_of(hits):
 
 def v_of(hits):
     return hits[:, 3]
+
+
+# ---- views of an (n, 12) or (n, 16) surface tensor
+
+
+def position(surf):
+    """The hit point re-projected onto its triangle, (n, 3); 1e11 on a miss."""
+    return surf[:, 0:3]
+
+
+def offset(surf):
+    """The reference's ray offset at the hit, (n,); 1e-7 on a miss."""
+    return surf[:, 3]
+
+
+def normal(surf):
+    """The geometric normal facing the ray, (n, 3); (0, -1, 0) on a miss."""
+    return surf[:, 4:7]
+
+
+def normal_dot_dir(surf):
+    """dot(normal, direction), <= 0, (n,)."""
+    return surf[:, 7]
+
+
+def shading_normal(surf):
+    """The interpolated vertex normal on the geometric normal's side, (n, 3); (0, -1, 0) on a miss."""
+    return surf[:, 8:11]
+
+
+def word(surf):
+    """The material / front-face / hit word as int32, (n,)."""
+    import torch
+
+    return surf.view(torch.int32)[:, 11]
+
+
+def material(surf):
+    """The material id the path tracer reads for the hit triangle, int32 (n,); 0 on a miss."""
+    return word(surf) & 0xFFFF
+
+
+def front_face(surf):
+    """Whether the ray met the front of the triangle, bool (n,); False on a miss."""
+    return (word(surf) & (1 << 16)) != 0
+
+
+def is_hit(surf):
+    return (word(surf) & (1 << 17)) != 0
+
+
+def displacement(surf):
+    """How the hit point moved since the build before, (n, 3): only of (n, 16) records (motion=True)."""
+    if surf.shape[1] != 16:
+        raise ValueError("displacement needs the (n, 16) records of motion=True")
+    return surf[:, 12:15]
+
+
+def spawn_origins(surf, directions):
+    """Origins of secondary rays leaving the hits along `directions` (n, 3): pos + offset * normal, and
+    pos - offset * normal where the direction points through the surface (dot(direction, normal) < 0),
+    as the reference's reflection and refraction do.  A plain torch expression in float32: its roundings
+    are torch's, so unlike the records it makes no claim of bit parity with the reference."""
+    nrm = normal(surf)
+    side = ((directions[:, 0:3] * nrm).sum(1) < 0).to(surf.dtype) * -2.0 + 1.0
+    return position(surf) + (offset(surf) * side)[:, None] * nrm
