@@ -1153,6 +1153,92 @@ typedef struct rt_surface_query {
     uint32_t flags;
 } rt_surface_query;
 int rt_trace_surfaces_device(rt_context* ctx, const rt_surface_query* q);
+
+/* Closest-point queries (no reference counterpart): for points in caller-owned device memory, the
+ * nearest triangle of the current build and the nearest point on it, for sphere and capsule colliders,
+ * penetration depth, distance-field sampling, foot and hand placement on skinned meshes and proximity
+ * sensors: the proximity question no ray answers.  A best-first descent of the two-level LBVH by box
+ * distance (csrc/closest_points.hip), not a variant of the ray traversal.
+ *
+ * The rule (csrc/closest_kernels.h is the definition, compiled for host and device alike): plain fp32,
+ * one rounding per operation, nothing fused.  The closest point of triangle (v1, v2, v3) to p by
+ * Ericson's Voronoi-region walk in its branch order: vertex 1, vertex 2, edge 12, vertex 3, edge 31,
+ * edge 23, face.  With ab = v2 - v1, ac = v3 - v1, dot(a, b) = (ax bx + ay by) + az bz, d1 = dot(ab, p - v1),
+ * d2 = dot(ac, p - v1), d3 = dot(ab, p - v2), d4 = dot(ac, p - v2), d5 = dot(ab, p - v3), d6 = dot(ac, p - v3),
+ * vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, the weights (wa, wb, wc) of (v1, v2, v3) are
+ *   d1 <= 0 and d2 <= 0                           vertex 1   (1, 0, 0)
+ *   d3 >= 0 and d4 <= d3                          vertex 2   (0, 1, 0)
+ *   vc <= 0, d1 >= 0, d3 <= 0                     edge 12    t = d1 / (d1 - d3): (1 - t, t, 0)
+ *   d6 >= 0 and d5 <= d6                          vertex 3   (0, 0, 1)
+ *   vb <= 0, d2 >= 0, d6 <= 0                     edge 31    t = d2 / (d2 - d6): (1 - t, 0, t)
+ *   va <= 0, d4 - d3 >= 0, d5 - d6 >= 0           edge 23    t = (d4 - d3) / ((d4 - d3) + (d5 - d6)): (0, 1 - t, t)
+ *   otherwise                                     face       r = 1 / ((va + vb) + vc); wb = vb r clamped to
+ *                                                            [0, 1]; wc = vc r clamped to [0, 1 - wb];
+ *                                                            wa = (1 - wb) - wc
+ * (the clamps change nothing while va, vb, vc > 0; they keep the point on the triangle when a sliver's
+ * rounding reaches the face otherwise, and let a NaN through).  The point is, per component,
+ * c = (v1 wa + v2 wb) + v3 wc; d = p - c; d2 = (dx dx + dy dy) + dz dz; u = wa, v = wb: the hit records'
+ * barycentrics, so a per-vertex quantity is q1 u + q2 v + q3 (1 - u - v) as for a surface record.  The
+ * front bit is dot(n, p - v1) > 0 with n = (aby acz - abz acy, abz acx - abx acz, abx acy - aby acx).  A
+ * triangle whose d2 is a NaN is no candidate: one with a vertex that is not finite, or one of zero area
+ * that reaches the face's 1 / 0.
+ *
+ * The answer: the candidates are the triangles that are leaves of the build's tree (what a ray can hit:
+ * per 1024-triangle batch the first `count` entries of RT_ARR_REORDER) with an index below the build's
+ * triangle count.  The up to three padding triangles that sort into the last batch are no candidates,
+ * and the real triangles they displace from the tree are absent, as they are for rays.  (A last batch
+ * of one leaf stores its first triangle as that leaf whatever sorted first; the list is the definition,
+ * so that triangle is a candidate only when the list names it.)  The answer is
+ * the candidate with the lexicographically smallest (d2, triangle index) among those with
+ * d2 <= max_distance * max_distance (the product in fp32; +inf stays +inf).  It does not depend on the
+ * traversal: rt_closest_points_host over those triangles gives the same bits.  A point with a coordinate
+ * that is not finite, no candidate, or none within max_distance gives the miss record.
+ *
+ * The record, RT_CLOSEST_FLOATS floats per point, as two 16-byte quads:
+ *   quad  .x .y .z                                              .w
+ *   0     the closest point (miss: RayMax x 3)                   d2 (miss: +inf)
+ *   1     triangle index as int32 bits (miss: -1), u, v          uint32 bits: 0..2 the feature (0 face, 1 2 3
+ *         (miss: 0, 0)                                           vertex 1 2 3, 4 edge 12, 5 edge 23, 6 edge 31),
+ *                                                                16 front, 17 found; a miss: 0
+ *
+ * Ordering: everything rt_trace_rays_device documents.  The kernel runs on the context stream behind
+ * ready_event, on the build current at the call, whose LBVH set it holds against later builds; the host
+ * is never synchronised, no stream is drained, what a synchronous draw traced ahead is kept, and the
+ * path tracer's workspace, RT_ARR_PT_QUEUE and rt_get_ray_count are left as they were.  n == 0 is
+ * RT_OK and enqueues nothing but done_event.  A context that never calls it allocates and launches
+ * nothing for it.
+ *
+ * RT_ERR_ARG: NULL ctx or q (checked first); then, before the init state: a stride below 3,
+ * n > RT_QUERY_MAX_RAYS, a max_distance that is negative or a NaN, and with n > 0 a NULL points or out,
+ * points not 4-byte or out not 16-byte aligned.  RT_ERR_STATE before rt_init (and before the first
+ * build); RT_ERR_HIP for a failed launch.  It never returns RT_ERR_DEVICE.
+ *
+ * Not provided: a signed distance (the sign near edges and vertices needs angle-weighted pseudo-normals;
+ * the front bit is the sign only where the feature is the face), per-point radii (one max_distance per
+ * call), the k nearest triangles, a host-buffer variant of the device query.
+ *
+ * [debug] closestStack = N (2..32, default 32) lowers the per-point stack of the descent.  A push onto a
+ * full stack makes that point's answer come from a scan of the build's leaf list instead: the same
+ * answer, slowly; trees deeper than the stack (chains of equal Morton keys) take that path too. */
+#define RT_CLOSEST_FLOATS 8u
+#define RT_CLOSEST_FRONT (1u << 16)
+#define RT_CLOSEST_FOUND (1u << 17)
+typedef struct rt_closest_query {
+    const float* points; uint32_t stride;  /* device; stride in floats, >= 3; 4-byte aligned */
+    uint32_t n;                            /* <= RT_QUERY_MAX_RAYS; 0 is RT_OK, only done_event */
+    float max_distance;                    /* >= 0 or +inf; NaN or negative: RT_ERR_ARG */
+    float* out;                            /* device, 16-byte aligned, n x 8 floats */
+    void* ready_event; void* done_event;   /* as rt_ray_query */
+} rt_closest_query;
+int rt_closest_points_device(rt_context* ctx, const rt_closest_query* q);
+/* The rule and the definition on the host: no context, no device.  rt_point_triangle: the record of p
+ * against the one triangle xyz (v1, v2, v3), with index 0.  rt_closest_points_host: exhaustive; the rule
+ * for every triangle of tris (ntri x 9 floats) and every point (n x 3), triangle t under the index ids[t]
+ * (NULL: t; 0xFFFFFFFF is RT_ERR_ARG), the lower index winning a tie; out is n x 8 floats.  RT_ERR_ARG:
+ * a NULL array that is read or written, a negative or NaN max_distance. */
+int rt_point_triangle(const float p[3], const float xyz[9], float out8[8]);
+int rt_closest_points_host(const float* tris, const uint32_t* ids, uint32_t ntri, const float* points, uint32_t n,
+                           float max_distance, float* out);
 size_t rt_array_bytes(const rt_context* ctx, int what);
 
 #ifdef __cplusplus

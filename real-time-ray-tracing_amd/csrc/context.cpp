@@ -455,6 +455,21 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
     ctx->bvhSkipPublish = (uint32_t)rttoml::find_or_int(doc, "debug", "bvhSkipPublish", -1);
     ctx->bvhSkipBuilds = rttoml::find_or_int(doc, "debug", "bvhSkipPublishBuilds", -1);
     ctx->bvhWaitMs = rttoml::find_or_float(doc, "debug", "bvhWaitMs", 1000.0f);
+    if (const rttoml::Value* v = rttoml::find(doc, "debug", "closestStack")) {
+        char* end = nullptr;
+        const long cap = v->isArray || v->isString || v->raw.empty() ? -1 : strtol(v->raw.c_str(), &end, 10);
+        if (!end || *end != '\0') {
+            g_createError = "config parse error: [debug] closestStack must be an integer";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        if (cap < 2 || cap > 32) {  // kClosestStackMax (frame_kernels.h)
+            g_createError = "[debug] closestStack must be 2..32";
+            delete ctx;
+            return RT_ERR_ARG;
+        }
+        ctx->closestStack = (int)cap;
+    }
     {
         rt_context::Tuning& t = ctx->tune;
         t.arena = rttoml::find_or_bool(doc, "tuning", "arena", true);

@@ -279,6 +279,7 @@ struct rt_context {
     uint32_t bvhSkipPublish = 0xFFFFFFFFu;
     int bvhSkipBuilds = -1;  // [debug] bvhSkipPublishBuilds: the fault applies to this many builds (-1: all)
     float bvhWaitMs = 1000.0f;
+    int closestStack = 32;   // [debug] closestStack: stack entries of a closest-point query's lanes (2..kClosestStackMax)
     uint32_t buildSeq = 0;   // LBVH builds issued so far (a timeout report names the build)
     // [tuning] scheduling knobs (A/B aids, config only; the defaults are the measured best,
     // DESIGN.md §7): the device-buffer arena, plain prioritised streams instead of CU-masked ones,
@@ -552,6 +553,7 @@ extern "C" int copy_rgba_out(rt_context* ctx, void* dst);  // frame.cpp: the las
 extern "C" size_t rt_alloc_bytes(const rt_context* ctx, int name);  // frame.cpp: allocated size of a render buffer
 int alloc_bvh_set(rt_context* ctx, BvhBufs& b);  // context.cpp: an LBVH set's buffers, arena cleared and placed
 int build_bvh(rt_context* ctx, int set, hipStream_t stream);  // context.cpp: the LBVH of the current geometry into bvh[set]
+bool closest_distance_ok(float max_distance);  // closest.cpp
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
 extern "C" int ensure_emitter_lists(rt_context* ctx);  // context.cpp: the existing LBVH sets' emitter-list buffers
 inline bool emitter_active(const rt_context* ctx) { return ctx->emitterOn && ctx->matCustom && ctx->matEmits; }

@@ -1982,3 +1982,48 @@ int rt_trace_surfaces_device(rt_context* ctx, const rt_surface_query* q) {
     if (r->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)r->done_event, s));
     return RT_OK;
 }
+
+// Closest-point queries (closest_points.hip): the nearest triangle of the current build for caller points
+// in device memory, by the rule of closest_kernels.h.  Ordering and state are the ray query's: the
+// context stream, behind ready_event and the current set's build, the set held against later builds, no
+// host synchronisation, nothing of the path tracer's touched.  Check order: NULL ctx / q, then the
+// other argument checks, then the init state.
+static const char* closest_query_fault(const rt_closest_query* q) {
+    if (q->stride < 3u) return "stride is in floats and at least 3";
+    if (q->n > RT_QUERY_MAX_RAYS) return "more points than RT_QUERY_MAX_RAYS";
+    if (!closest_distance_ok(q->max_distance)) return "max_distance must be >= 0 or +inf";
+    if (q->n > 0u && (!q->points || !q->out)) return "points and out must not be NULL";
+    if (q->n > 0u && ((uintptr_t)q->points & 3u) != 0) return "points must be 4-byte aligned";
+    if (q->n > 0u && ((uintptr_t)q->out & 15u) != 0) return "out must be 16-byte aligned";
+    return nullptr;
+}
+
+int rt_closest_points_device(rt_context* ctx, const rt_closest_query* q) {
+    if (!ctx || !q) return RT_ERR_ARG;
+    if (const char* bad = closest_query_fault(q)) { ctx->err = std::string("rt_closest_points_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_closest_points_device before rt_init"; return RT_ERR_STATE; }
+    hipStream_t s = ctx->stream;
+    if (q->n > 0u) {
+        if (q->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)q->ready_event, 0));
+        if (int rc = wait_bvh(ctx)) return rc;  // the current set's build, wherever it ran
+        BvhBufs& b = ctx->lbvh();
+        if (b.B == 0u || b.triCount == 0u) { ctx->err = "rt_closest_points_device before the first rt_build_bvh"; return RT_ERR_STATE; }
+        ClosestParams p;
+        p.nodes = b.nodes;
+        p.tlasNodes = b.tlasNodes;
+        p.triPos = b.triPos;
+        p.reorder = b.reorder;
+        p.triCount = b.triCount;
+        p.batchCount = b.B;
+        p.points = q->points;
+        p.stride = q->stride;
+        p.n = q->n;
+        p.limit = q->max_distance * q->max_distance;  // fp32 (-ffp-contract=off): closest_limit
+        p.stackCap = (uint32_t)ctx->closestStack;
+        p.out = q->out;
+        HIP_TRY(ctx, rtk_launch_closest_points(&p, s));
+        if (int rc = hold_query_set(ctx, b, s)) return rc;
+    }
+    if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));
+    return RT_OK;
+}

@@ -410,3 +410,22 @@ struct RaySurfaceParams {
 };
 // grid: ceil(n / 256) workgroups, one thread per ray; motion: the four-quad record
 extern "C" hipError_t rtk_launch_ray_surface(const RaySurfaceParams* p, int motion, hipStream_t stream);
+
+// One closest-point query (closest_points.hip, rt_closest_points_device): caller points in, one 32-B
+// record per point out (closest_kernels.h: the rule, the record, the pruning bound)
+constexpr int kClosestStackMax = 32;  // stack entries per lane in LDS ([debug] closestStack lowers the number used)
+struct ClosestParams {
+    const void* nodes;        // the LBVH set, as RayQueryParams
+    const void* tlasNodes;
+    const float4* triPos;
+    const uint32_t* reorder;  // [batchCount * 1024] the build's leaf list: batch b's leaves are b * 1024 + reorder[b * 1024 + k]
+    uint32_t triCount, batchCount;  // of the set's build (batchCount >= 1)
+    const float* points;      // point i at points + i * stride
+    uint32_t stride;          // in floats, >= 3
+    uint32_t n;               // 1 .. RT_QUERY_MAX_RAYS
+    float limit;              // max_distance squared in fp32 (closest_limit)
+    uint32_t stackCap;        // 2 .. kClosestStackMax
+    float* out;               // [n][8], 16-byte aligned
+};
+// grid: ceil(n / 128) workgroups, one thread per point
+extern "C" hipError_t rtk_launch_closest_points(const ClosestParams* p, hipStream_t stream);

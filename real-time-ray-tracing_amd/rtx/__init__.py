@@ -108,6 +108,12 @@ class SurfaceQuery(C.Structure):
     _fields_ = [("rays", RayQuery), ("surface", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class ClosestQuery(C.Structure):
+    """rt_closest_query: one device closest-point query (rt_closest_points_device)."""
+    _fields_ = [("points", C.c_void_p), ("stride", C.c_uint32), ("n", C.c_uint32), ("max_distance", C.c_float),
+                ("out", C.c_void_p), ("ready_event", C.c_void_p), ("done_event", C.c_void_p)]
+
+
 class Mesh(C.Structure):
     """rt_mesh: an indexed mesh for rt_set_mesh / rt_set_mesh_device."""
     _fields_ = [("xyz", C.c_void_p), ("vertex_count", C.c_uint32), ("indices", C.c_void_p),
@@ -173,6 +179,10 @@ QUERY_MAX_RAYS = 1 << 30   # RT_QUERY_MAX_RAYS
 SURFACE_FROM_HITS, SURFACE_MOTION = 1, 2  # RT_SURFACE_*
 
 
+CLOSEST_FLOATS = 8                           # RT_CLOSEST_FLOATS
+CLOSEST_FRONT, CLOSEST_FOUND = 1 << 16, 1 << 17  # RT_CLOSEST_*: bits of a closest-point record's last word
+
+
 def surface_floats(flags: int) -> int:
     """RT_SURFACE_FLOATS: floats per ray of a surface record."""
     return 16 if flags & SURFACE_MOTION else 12
@@ -223,6 +233,9 @@ SIGNATURES = {
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayQuery)]),
     "rt_trace_surfaces_device": (C.c_int, [C.c_void_p, C.POINTER(SurfaceQuery)]),
+    "rt_closest_points_device": (C.c_int, [C.c_void_p, C.POINTER(ClosestQuery)]),
+    "rt_point_triangle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_closest_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "rt_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rt_array_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "rt_save_camera": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -971,6 +984,20 @@ class RayTracer:
         q = SurfaceQuery(rays, surface_ptr, (SURFACE_FROM_HITS if from_hits else 0) | (SURFACE_MOTION if motion else 0))
         self._check(self.lib.rt_trace_surfaces_device(self.h, C.byref(q)), "rt_trace_surfaces_device")
 
+    def closest_points_device(self, points_ptr: int, n: int, out_ptr: int, *, stride: int = 3,
+                              max_distance: float = float("inf"), ready_event: int | None = None,
+                              done_event: int | None = None):
+        """rt_closest_points_device: for n points in device memory (point i at points_ptr + 4 * i * stride
+        bytes) the nearest triangle of the current build within max_distance, as n records of 8 float32 at
+        out_ptr: the closest point and the squared distance, then the triangle index bits, u, v and the
+        feature / front / found word.  Enqueued on the context stream; the host is not synchronised.
+        ready_event / done_event as in trace_rays_device.  rtx.query.closest is the torch-tensor form."""
+        for name, v in (("n", n), ("stride", stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("closest_points_device: %s must fit 32 bits" % name)
+        q = ClosestQuery(points_ptr, int(stride), int(n), float(max_distance), out_ptr, ready_event, done_event)
+        self._check(self.lib.rt_closest_points_device(self.h, C.byref(q)), "rt_closest_points_device")
+
     def get_buffer(self, name: str, shape=None, dtype=np.uint8) -> np.ndarray:
         if shape is None:
             n = self.lib.rt_buffer_bytes(self.h, BUF[name])
@@ -1065,6 +1092,42 @@ def skin_vertices(rest, joints, weights, matrices) -> np.ndarray:
     rc = load_library().rt_skin_vertices(C.byref(s), m.ctypes.data, out.ctypes.data)
     if rc != RT_OK:
         raise RtError("rt_skin_vertices: %s" % ERRORS.get(rc, rc))
+    return out
+
+
+def point_triangle(p, triangle) -> np.ndarray:
+    """rt_point_triangle: the closest-point rule on the host (no context, no device) for one point and one
+    triangle ((3, 3): v1, v2, v3): the 8-float record with triangle index 0, bit for bit the device's."""
+    p = np.ascontiguousarray(p, np.float32)
+    t = np.ascontiguousarray(triangle, np.float32)
+    if p.shape != (3,) or t.size != 9:
+        raise ValueError("point_triangle: p is (3,), triangle is (3, 3)")
+    out = np.zeros(8, np.float32)
+    rc = load_library().rt_point_triangle(p.ctypes.data, t.ctypes.data, out.ctypes.data)
+    if rc != RT_OK:
+        raise RtError("rt_point_triangle: %s" % ERRORS.get(rc, rc))
+    return out
+
+
+def closest_points_host(triangles, points, *, ids=None, max_distance: float = float("inf")) -> np.ndarray:
+    """rt_closest_points_host: the definition of a closest-point query's answer, exhaustively on the host:
+    triangles (ntri, 3, 3), points (n, 3), ids (ntri,) the index each triangle is reported under (None:
+    its row).  Returns the (n, 8) float32 records; on equal squared distances the lower id wins."""
+    t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
+    p = np.ascontiguousarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("closest_points_host: points is (n, 3)")
+    i = None
+    if ids is not None:
+        i = np.ascontiguousarray(ids, np.uint32)
+        if i.shape != (len(t),):
+            raise ValueError("closest_points_host: ids holds one index per triangle")
+    out = np.zeros((len(p), 8), np.float32)
+    rc = load_library().rt_closest_points_host(t.ctypes.data if len(t) else None, None if i is None else i.ctypes.data,
+                                               len(t), p.ctypes.data if len(p) else None, len(p),
+                                               float(max_distance), out.ctypes.data if len(p) else None)
+    if rc != RT_OK:
+        raise RtError("rt_closest_points_host: %s" % ERRORS.get(rc, rc))
     return out
 
 

@@ -12,6 +12,11 @@ build before (views: ``position`` .. ``is_hit``).  ``surfaces(rt, origins, direc
 the same records from the hit records of an earlier query, without a traversal.  ``spawn_origins``
 gives the origins of secondary rays, so that query -> surfaces -> second query runs on the device.
 
+``closest(rt, points)`` answers the proximity question no ray does: per point the nearest triangle of
+the current build and the nearest point on it (rt_closest_points_device), one (n, 8) record per point
+(views: ``closest_position`` .. ``closest_found``), for colliders, penetration depth, distance-field
+sampling and placement on skinned meshes.
+
 The query runs on the renderer's stream (``set_stream``).  ``trace`` may be called from any torch
 stream: it hands the renderer an event recorded on ``torch.cuda.current_stream()`` to wait for, and
 makes that stream wait for the query's end, so tensors filled just before the call are read after
@@ -136,6 +141,44 @@ def surfaces(rt, origins, directions, hits, *, motion: bool = False, out=None):
     return surf
 
 
+def closest(rt, points, *, max_distance: float = float("inf"), out=None):
+    """Closest-point records of the points (points[i, :3]) against the build that is current now.
+
+    points: a float32 device tensor of shape (n, 3..8) with a unit inner stride, read in place as the
+    rays of ``trace`` are.  max_distance: >= 0 or inf; a point with nothing within it gets the miss
+    record.  out: a contiguous (n, 8) float32 tensor for the records.
+
+    Returns (n, 8) float32: the closest point (1e11 x 3 on a miss), the squared distance (inf), the
+    triangle index as int32 bits (-1), u, v (the weights of the triangle's first two vertices) and the
+    feature / front / found word (see the ``closest_*`` views).  Same event protocol as ``trace``."""
+    import torch
+
+    n, stride = _rays("points", points, torch)
+    if n > (1 << 30):
+        raise ValueError("at most 2^30 points per query")
+    if not max_distance >= 0.0:
+        raise ValueError("max_distance must be >= 0 or inf")
+    _dense("out", out, (n, 8), torch)
+    if not points.is_cuda:
+        raise ValueError("points must be on the renderer's device, not on %s" % points.device)
+    dev = points.device
+    if out is not None and out.device != dev:
+        raise ValueError("points, out must be on one device")
+    dev_id = rt.info().deviceId
+    if dev_id >= 0 and dev.index is not None and dev.index != dev_id:
+        raise ValueError("the points are on %s, the renderer on device %d" % (dev, dev_id))
+    cur = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        rec = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=dev)
+        ready, done = torch.cuda.Event(), torch.cuda.Event()
+        ready.record(cur)
+        done.record(cur)  # creates the handle; the renderer records it again behind the kernel
+        rt.closest_points_device(points.data_ptr(), n, rec.data_ptr(), stride=stride, max_distance=max_distance,
+                                 ready_event=ready.cuda_event, done_event=done.cuda_event)
+        cur.wait_event(done)
+    return rec
+
+
 def split(hits):
     """(t, tri, u, v) views of an (n, 4) hit tensor; tri is int32, -1 on a miss."""
     return t_of(hits), tri_of(hits), u_of(hits), v_of(hits)
@@ -223,3 +266,49 @@ def spawn_origins(surf, directions):
     nrm = normal(surf)
     side = ((directions[:, 0:3] * nrm).sum(1) < 0).to(surf.dtype) * -2.0 + 1.0
     return position(surf) + (offset(surf) * side)[:, None] * nrm
+
+
+# ---- views of an (n, 8) closest-point tensor
+
+
+def closest_position(rec):
+    """The nearest point of the nearest triangle, (n, 3); 1e11 on a miss."""
+    return rec[:, 0:3]
+
+
+def distance2(rec):
+    """The squared distance to it, (n,); inf on a miss."""
+    return rec[:, 3]
+
+
+def closest_tri(rec):
+    """The triangle index as int32, (n,); -1 on a miss."""
+    import torch
+
+    return rec.view(torch.int32)[:, 4]
+
+
+def closest_uv(rec):
+    """(u, v), (n, 2): the weights of the triangle's first and second vertex, the third's is 1 - u - v."""
+    return rec[:, 5:7]
+
+
+def closest_word(rec):
+    """The feature / front / found word as int32, (n,)."""
+    import torch
+
+    return rec.view(torch.int32)[:, 7]
+
+
+def closest_feature(rec):
+    """0 face, 1 2 3 vertex 1 2 3, 4 edge 12, 5 edge 23, 6 edge 31; int32 (n,), 0 on a miss."""
+    return closest_word(rec) & 7
+
+
+def closest_front(rec):
+    """Whether the point lies on the side the triangle's normal (v2 - v1) x (v3 - v1) points to, bool (n,)."""
+    return (closest_word(rec) & (1 << 16)) != 0
+
+
+def closest_found(rec):
+    return (closest_word(rec) & (1 << 17)) != 0
