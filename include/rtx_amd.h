@@ -46,7 +46,8 @@ typedef struct rt_context rt_context;
  * geometryMotion (true | false, default false: rt_set_geometry_motion's initial state; any other
  * value is refused with RT_ERR_IO), [render] emitterSampling (true | false, default false) and [render]
  * emitterProbability (a number in [0, 1], default 0.5): rt_set_emitter_sampling's initial state; an
- * unparsable or out-of-range value is refused with RT_ERR_IO.
+ * unparsable or out-of-range value is refused with RT_ERR_IO.  [render] signedDistance (true | false,
+ * default false: rt_set_signed_distance's initial state; any other value is refused with RT_ERR_IO).
  * [tuning] (scheduling A/B aids; the defaults are the measured best): arena (bool),
  * streams ("cumask" | "prio"), tracePerCu / trace4PerCu (0: automatic), trace3ShortPerCu (a short queue
  * 3's workgroups per CU on one GPU; 0: all of them), chain ("serial" | "off" |
@@ -1036,12 +1037,15 @@ enum rt_array_name {
                                     to P, the power of two >= max(triCount, 256); P from rt_array_bytes */
     RT_ARR_PT_Q3_BETA = 49,      /* float4[cap] step-3 queue: the first diffuse interaction's throughput beta1 xyz,
                                     ray-cone spread ([0] of RT_ARR_PT_QUEUE are valid) */
-    RT_ARR_SPEC_STATS = 50       /* uint32[4] the synchronous draws' launches ahead (rt_draw), counted on the host
+    RT_ARR_SPEC_STATS = 50,      /* uint32[4] the synchronous draws' launches ahead (rt_draw), counted on the host
                                     since rt_init: [0] launched, [1] reused by the next draw, [2] dropped unused
                                     (the next draw's launch parameters differed, the sky tables were regenerated,
                                     or a call waited for the streams), [3] 1 while one awaits the next draw;
                                     [0] == [1] + [2] + [3].  Host state: the read waits for nothing and drops
                                     nothing.  All zero with [tuning] syncSpec off; pipelined frames add nothing */
+    RT_ARR_PSEUDO_NORMALS = 51   /* float4[triCount][6] the pseudo-normal table of the last LBVH build
+                                    (rt_set_signed_distance): per triangle vertex 1 2 3, edge 12 23 31, .w = 0;
+                                    size 0 while that build wrote none */
 };
 /* RT_ARR_TEX_ALBEDO_AO and RT_ARR_TEX_NORMAL_ROUGHNESS OR-ed with RT_ARR_TEX_SET(k) name the chain of
  * texture set k (k = 0 is the plain name); a k past the context's sets is RT_ERR_ARG (rt_array_bytes: 0). */
@@ -1213,8 +1217,8 @@ int rt_trace_surfaces_device(rt_context* ctx, const rt_surface_query* q);
  * points not 4-byte or out not 16-byte aligned.  RT_ERR_STATE before rt_init (and before the first
  * build); RT_ERR_HIP for a failed launch.  It never returns RT_ERR_DEVICE.
  *
- * Not provided: a signed distance (the sign near edges and vertices needs angle-weighted pseudo-normals;
- * the front bit is the sign only where the feature is the face), per-point radii (one max_distance per
+ * The distance is unsigned, and the front bit is its sign only where the feature is the face: a
+ * signed distance is rt_signed_distance_device's (below).  Not provided: per-point radii (one max_distance per
  * call), the k nearest triangles, a host-buffer variant of the device query.
  *
  * [debug] closestStack = N (2..32, default 32) lowers the per-point stack of the descent.  A push onto a
@@ -1239,6 +1243,92 @@ int rt_closest_points_device(rt_context* ctx, const rt_closest_query* q);
 int rt_point_triangle(const float p[3], const float xyz[9], float out8[8]);
 int rt_closest_points_host(const float* tris, const uint32_t* ids, uint32_t ntri, const float* points, uint32_t n,
                            float max_distance, float* out);
+
+/* Signed distance queries (no reference counterpart): the closest-point query with "inside or outside",
+ * for penetration depth, distance-field sampling and inside tests against closed meshes that are
+ * animated, skinned or streamed, without a host wait.  The closest record's front bit is the sign only
+ * where the nearest feature is a face; at an edge or a vertex the lowest-index triangle wins the tie and
+ * the point may lie behind its plane while outside the solid.  The sign here comes from angle-weighted
+ * pseudo-normals (Baerentzen and Aanaes 2005): the sign of dot(N, p - c) with N the pseudo-normal of the
+ * nearest feature is the inside / outside answer of a closed, consistently wound, welded mesh.
+ *
+ * The rule (csrc/sdf_kernels.h is the definition, compiled for host and device alike): plain fp32, one
+ * rounding per operation, nothing fused, dot(a, b) = (ax bx + ay by) + az bz.
+ *   unit normal of (v1, v2, v3): n = ab x ac as the closest rule's front bit computes it;
+ *     l2 = dot(n, n); if l2 > 0 is false or l2 is not finite the triangle is degenerate: it contributes
+ *     nothing anywhere and its own unit normal is (0, 0, 0); otherwise n / sqrtf(l2) per component.
+ *   corner angle: rt_acosf(clamp(dot(ea, eb) / sqrtf(dot(ea, ea) dot(eb, eb)), -1, 1)); a NaN stays a NaN,
+ *     and such a corner contributes nothing to its vertex.  Corner 1: ea = v2 - v1, eb = v3 - v1;
+ *     corner 2: v3 - v2, v1 - v2; corner 3: v1 - v3, v2 - v3.
+ *   vertex pseudo-normal of vertex id a: acc = +0; over the slots of a in rt_mesh_adjacency's order
+ *     (ascending corner index c, t' = c / 3), skipping t' >= triCount, degenerate triangles and NaN angles:
+ *     acc = acc + angle * unit(t') per component, the product rounded first.
+ *   edge pseudo-normal of the edge (a, b): the same walk over the slots of a; for a counted t' that
+ *     carries b at another of its corners, acc = acc + unit(t').  The walk meets the triangles in ascending
+ *     index from either end, so the triangles that share an edge hold the same bits for it.  A boundary
+ *     edge gets its own triangle's unit normal, an edge of three or more triangles the sum of them all.
+ * The table of a build holds, per triangle t < triCount, six float4 (.w = 0) in the order of the closest
+ * record's feature codes 1..6: vertex 1, 2, 3, edge 12 (a = i1, b = i2), edge 23 (i2, i3), edge 31
+ * (i3, i1).  All triangles below triCount contribute, whether or not padding displaced them from the
+ * tree; the padding triangles have all indices 0, are degenerate and drop out.  Positions are the
+ * vertices the build gathered.  Vertex identity is the index: a mesh that repeats positions under
+ * several indices (unwelded) or winds neighbours inconsistently gets per-index pseudo-normals that mean
+ * little.  Welding is the caller's job.
+ *
+ * The sign record, one 16-byte quad per point, from the point p and its closest record: N is the table
+ * entry of (triangle, feature), for the face (feature 0) the triangle's unit normal from the set's
+ * triangle record; d = p - c per component, c the record's closest point; s = dot(N, d);
+ *   .xyz = N (not normalised; all zero: no incident triangle counted)
+ *   .w   = sqrtf(d2), negated when s < 0 (a zero or NaN s reads as outside); d2 is the record's
+ * A miss record gives (0, 0, 0, +inf).
+ *
+ * rt_set_signed_distance(ctx, on) is a host-style setter like rt_set_emitter_sampling: it waits for the
+ * streams, drops what a synchronous draw built or traced ahead, and takes effect from the next LBVH
+ * build.  The first enable allocates 96 B per triangle of the capacity (the table) and 72 B per padded
+ * triangle (the table build's scratch) on each LBVH set that exists; sets created later get theirs when
+ * they are created.  While on, every build writes its set's table behind it on the build's stream
+ * (csrc/sdf.hip: a triangle pass into the vertex -> corner adjacency's slots and a gather pass; no float
+ * atomics), so frames in flight and held query sets keep the table of their build, and a later vertex
+ * update or mesh set is ordered behind the read.  rt_download(RT_ARR_PSEUDO_NORMALS) reads the table of
+ * the last build.  RT_ERR_ARG: NULL ctx (or NULL on); RT_ERR_STATE: before rt_init.
+ *
+ * rt_signed_distance_device runs rt_closest_points_device's descent unchanged, which writes the closest
+ * records to closest.out, and behind it on the context stream a dense sign pass (one lane per point)
+ * that writes the quads to signed_out.  With RT_DISTANCE_FROM_RECORDS nothing descends: closest.out is
+ * read as the records of an earlier query on the same points and the same build (that it is the same
+ * build is the caller's responsibility); a record whose triangle index is not below the build's triangle
+ * count, -1 included, or whose feature code is past 6, is finished as a miss.  Ordering is the closest
+ * query's: closest.ready_event is waited for ahead of the descent, closest.done_event is recorded behind
+ * the sign pass, the LBVH set is held until the pass has read it, and the host is never synchronised.
+ *
+ * Errors, in this order: RT_ERR_ARG for a NULL ctx or q; RT_ERR_ARG for every argument error of
+ * rt_closest_points_device on q->closest, unknown flag bits, and with n > 0 a NULL or not 16-byte aligned
+ * signed_out; RT_ERR_STATE before rt_init, or when the current build wrote no table (the feature is off,
+ * or it was enabled after that build), n == 0 included; RT_ERR_HIP for a failed launch.  Never
+ * RT_ERR_DEVICE.  With a table, n == 0 is RT_OK and enqueues nothing but done_event.
+ *
+ * Not provided: per-point radii, the k nearest triangles, a host-buffer variant of the device query, a
+ * generalised winding number for open or unoriented meshes (there the sign follows the nearest
+ * feature's pseudo-normal, which means what the winding does). */
+int rt_set_signed_distance(rt_context* ctx, int on);
+int rt_get_signed_distance(const rt_context* ctx, int* on);
+#define RT_DISTANCE_FROM_RECORDS 1u   /* closest.out is input: no descent, only the sign pass */
+typedef struct rt_distance_query {
+    rt_closest_query closest;  /* as rt_closest_points_device; its records are written to closest.out */
+    float* signed_out;         /* device, 16-B aligned, n x 4 floats */
+    uint32_t flags;
+} rt_distance_query;
+int rt_signed_distance_device(rt_context* ctx, const rt_distance_query* q);
+/* The rule on the host: no context, no device.  rt_pseudo_normals: the table of a mesh (xyz:
+ * vertex_count x 3, indices: triangle_count x 3) into out (triangle_count x 24 floats), with the adjacency
+ * of rt_mesh_adjacency over the given triangles; RT_ERR_ARG for a NULL pointer, a zero count or an index
+ * >= vertex_count.  rt_signed_distance_rule: the sign record of p from its closest record rec8, the named
+ * triangle's positions xyz9 (v1, v2, v3) and its six table entries pn24; a miss record (the found bit
+ * clear, index -1 or a feature code past 6) gives (0, 0, 0, +inf); RT_ERR_ARG for a NULL pointer. */
+int rt_pseudo_normals(const float* xyz, uint32_t vertex_count, const uint32_t* indices, uint32_t triangle_count,
+                      float* out /* triangle_count x 24 */);
+int rt_signed_distance_rule(const float p[3], const float rec8[8], const float xyz9[9], const float pn24[24],
+                            float out4[4]);
 size_t rt_array_bytes(const rt_context* ctx, int what);
 
 #ifdef __cplusplus

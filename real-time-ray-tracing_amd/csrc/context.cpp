@@ -271,8 +271,9 @@ int rt_event(rt_context* ctx, hipEvent_t& e, bool timing) {
 
 // The buffers of one LBVH set, by the capacity (rt_set_mesh), which without the config keys is the init
 // mesh: the record arena (traverse.h: BLAS nodes, TLAS nodes, triangle records, 64 B each) cleared and
-// laid out for the current mesh, the build's scratch and its zeroed launch counter.  The displacement
-// and emitter-list buffers are their features' (ensure_geometry_motion, ensure_emitter_lists).
+// laid out for the current mesh, the build's scratch and its zeroed launch counter.  The displacement,
+// emitter-list and pseudo-normal buffers are their features' (ensure_geometry_motion,
+// ensure_emitter_lists, ensure_sdf_tables).
 int alloc_bvh_set(rt_context* ctx, BvhBufs& b) {
     if (b.counter) return RT_OK;  // allocated last: the set is complete
     const size_t NP = ctx->capNP, B = ctx->capB;
@@ -327,27 +328,6 @@ int rt_scan_device(const float* in, float* out, float* tmp, int size, int block_
     if (e != hipSuccess) {
         g_createError = std::string("rt_scan_device: ") + hipGetErrorString(e);
         return RT_ERR_HIP;
-    }
-    return RT_OK;
-}
-
-// rt_init's vertex -> corner CSR (kernel.cu:313-327 walks it in triangle order) and its inverse; the
-// definition the device kernels of a mesh set reproduce (mesh.hip)
-int rt_mesh_adjacency(const uint32_t* indices, uint32_t padded_triangles, uint32_t vertex_count, uint32_t* adj_offsets,
-                      uint32_t* adj_corners, uint32_t* corner_slots) {
-    if (!indices || !adj_offsets || vertex_count == 0) return RT_ERR_ARG;
-    const size_t n = (size_t)padded_triangles * 3;
-    for (size_t c = 0; c < n; ++c)
-        if (indices[c] >= vertex_count) return RT_ERR_ARG;
-    for (size_t v = 0; v <= vertex_count; ++v) adj_offsets[v] = 0;
-    for (size_t c = 0; c < n; ++c) adj_offsets[(size_t)indices[c] + 1]++;
-    for (size_t v = 0; v < vertex_count; ++v) adj_offsets[v + 1] += adj_offsets[v];
-    if (!adj_corners && !corner_slots) return RT_OK;
-    std::vector<uint32_t> fill(adj_offsets, adj_offsets + vertex_count);
-    for (size_t c = 0; c < n; ++c) {
-        const uint32_t slot = fill[indices[c]]++;
-        if (corner_slots) corner_slots[c] = slot;
-        if (adj_corners) adj_corners[slot] = (uint32_t)c;
     }
     return RT_OK;
 }
@@ -441,6 +421,14 @@ int rt_create(int screen_width, int screen_height, const char* config_toml, rt_c
             return RT_ERR_IO;
         }
         ctx->emitterOn = v->raw == "true";
+    }
+    if (const rttoml::Value* v = rttoml::find(doc, "render", "signedDistance")) {
+        if (v->isArray || v->isString || (v->raw != "true" && v->raw != "false")) {
+            g_createError = "config parse error: [render] signedDistance must be true or false";
+            delete ctx;
+            return RT_ERR_IO;
+        }
+        ctx->sdfOn = v->raw == "true";
     }
     if (const rttoml::Value* v = rttoml::find(doc, "render", "emitterProbability")) {
         char* end = nullptr;
@@ -651,6 +639,7 @@ int rt_init(rt_context* ctx) {
     for (BvhBufs& b : ctx->bvh) RT_TRY(rt_event(ctx, b.queryDone));
     if (ctx->geomMotion) RT_TRY(ensure_geometry_motion(ctx));  // [render] geometryMotion
     if (ctx->emitterOn) RT_TRY(ensure_emitter_lists(ctx));     // [render] emitterSampling
+    if (ctx->sdfOn) RT_TRY(ensure_sdf_tables(ctx));            // [render] signedDistance
     // mesh sets (rt_set_mesh*, mesh.hip): the staging buffers of the host variants and the adjacency
     // sort's scratch, behind every other buffer of rt_init, so that a set only enqueues work
     RT_TRY(dalloc_once(ctx, ctx->dVertStage, capNV * 12));
@@ -870,6 +859,26 @@ int build_bvh(rt_context* ctx, int set, hipStream_t stream) {
         }
         b.emBuilt = true;
         b.emCdfLen = e.cdfLen;
+    }
+    // signed distance queries: the set's pseudo-normal table from the vertices this build has just gathered,
+    // behind it on its stream and ahead of buildDone.  The vertices, indices and adjacency are read where
+    // the build's gather and the displacement kernel read them, so a later vertex update or mesh set is
+    // behind this read as it is behind theirs, and whatever queries the set reads the table of its build.
+    b.sdfBuilt = false;
+    if (ctx->sdfOn && b.sdfSlotOthers && ctx->mesh.triCount > 0u) {
+        SdfTableParams t;
+        t.vertices = ctx->dVerts;
+        t.indices = ctx->dIdx;
+        t.cornerSlot = ctx->dCornerSlot;
+        t.adjOffsets = ctx->dAdjOff;
+        t.nverts = ctx->nv;
+        t.triCount = ctx->mesh.triCount;
+        t.triCountPadded = ctx->mesh.triCountPadded;
+        t.slotNormal = b.sdfSlotNormal;
+        t.slotOthers = b.sdfSlotOthers;
+        t.table = b.sdfTable;
+        HIP_TRY(ctx, rtk_launch_sdf_table(&t, stream));
+        b.sdfBuilt = true;
     }
     if (stream != ctx->stream) {  // the side stream: a pipelined frame's build, a synchronous draw's prebuild
         HIP_TRY(ctx, hipEventRecord(b.buildDone, stream));
@@ -1250,6 +1259,43 @@ int rt_get_emitter_sampling(const rt_context* ctx, int* on, float* probability) 
     if (!ctx || !on || !probability) return RT_ERR_ARG;
     *on = ctx->emitterOn ? 1 : 0;
     *probability = ctx->emitterQ;
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------- signed distance queries
+//
+// The pseudo-normal tables of the LBVH sets that exist (the second set's are allocated with it,
+// ensure_bvh_pair): 96 B per triangle of the capacity, and the table build's scratch, 24 B per corner of
+// the padded capacity.  Once allocated they stay.
+int ensure_sdf_tables(rt_context* ctx) {
+    for (BvhBufs& b : ctx->bvh)
+        if (b.nodes && !b.sdfSlotOthers) {
+            int rc;
+            if (!b.sdfTable && (rc = dalloc(ctx, &b.sdfTable, (size_t)ctx->capTri * 96)) != RT_OK) return rc;
+            if (!b.sdfSlotNormal && (rc = dalloc(ctx, &b.sdfSlotNormal, (size_t)ctx->capNP * 48)) != RT_OK) return rc;
+            if ((rc = dalloc(ctx, &b.sdfSlotOthers, (size_t)ctx->capNP * 24)) != RT_OK) return rc;  // last: the set is complete
+        }
+    return RT_OK;
+}
+
+int rt_set_signed_distance(rt_context* ctx, int on) {
+    if (!ctx) return RT_ERR_ARG;
+    if (!ctx->inited) { ctx->err = "rt_set_signed_distance before rt_init"; return RT_ERR_STATE; }
+    // what a synchronous draw traced ahead precedes the change
+    int rc = sync_streams(ctx, false);
+    if (rc != RT_OK) return rc;
+    if (on && (rc = ensure_sdf_tables(ctx)) != RT_OK) return rc;
+    // from the next build on: a synchronous draw's prebuild was made under the old state
+    ctx->bvhPrebuilt = false;
+    if (!on)
+        for (BvhBufs& b : ctx->bvh) b.sdfBuilt = false;
+    ctx->sdfOn = on != 0;
+    return RT_OK;
+}
+
+int rt_get_signed_distance(const rt_context* ctx, int* on) {
+    if (!ctx || !on) return RT_ERR_ARG;
+    *on = ctx->sdfOn ? 1 : 0;
     return RT_OK;
 }
 
@@ -1948,6 +1994,8 @@ size_t rt_array_bytes(const rt_context* ctx, int what) {
             return (size_t)count * 4;
         }
         case RT_ARR_EMITTER_CDF: return set.emBuilt ? (size_t)set.emCdfLen * 4 : 0;
+        // the pseudo-normal table of the current set's last build; nothing while that build wrote none
+        case RT_ARR_PSEUDO_NORMALS: return set.sdfBuilt ? (size_t)set.triCount * 96 : 0;
         case RT_ARR_TRI_MATERIALS: return (size_t)ctx->mesh.triCount;
         case RT_ARR_TRI_MATERIAL_CENSUS: return 256 * sizeof(uint32_t);
         case RT_ARR_SPEC_STATS: return 4 * sizeof(uint32_t);
@@ -2021,6 +2069,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         case RT_ARR_EMITTER_TRIS: src = set.emTris; break;
         case RT_ARR_EMITTER_WEIGHTS: src = set.emWeights; break;
         case RT_ARR_EMITTER_CDF: src = set.emCdf; break;
+        case RT_ARR_PSEUDO_NORMALS: src = set.sdfTable; break;
         case RT_ARR_SUN_DIR: {
             if (bytes < 16) { ctx->err = "destination too small"; return RT_ERR_ARG; }
             float* o = (float*)dst;
@@ -2066,7 +2115,7 @@ int rt_download(const rt_context* cctx, int what, void* dst, size_t bytes) {
         HIP_TRY(ctx, hipMemcpy2D(dst, 48, src, 64, 48, set.triCountPadded, hipMemcpyDeviceToHost));
         return RT_OK;
     }
-    if (need == 0) return RT_OK;  // an empty emitter list, or none
+    if (need == 0) return RT_OK;  // an empty emitter list, or none; no pseudo-normal table
     HIP_TRY(ctx, hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
     if (what == RT_ARR_NODES || what == RT_ARR_TLAS_NODES) {
         // the reference's q3 (idxLeft, idxRight, isLeftLeaf, isRightLeaf) from the child references

@@ -57,6 +57,13 @@ struct BvhBufs {
     float* emScanSums = nullptr;
     bool emBuilt = false;       // the set's last build wrote a list; the path traces on it sample emitters
     uint32_t emCdfLen = 0;      // ... whose CDF has this length (emitter_cdf_len of that build's triCount)
+    // signed distance queries (rt_set_signed_distance): the set's pseudo-normal table,
+    // written behind its build on the build's stream (sdf.hip), so every reader of the set reads the table
+    // of its build.  Allocated on the first enable, by the triangle capacity.
+    float4* sdfTable = nullptr;       // [capTri][6]
+    float4* sdfSlotNormal = nullptr;  // scratch of the table build, [capNP * 3]
+    uint2* sdfSlotOthers = nullptr;   // ... [capNP * 3]; allocated last: the set is complete
+    bool sdfBuilt = false;            // the set's last build wrote a table
     // the set's last build on the side stream (ensure_bvh_pair creates the events)
     hipEvent_t buildDone = nullptr;
     bool buildOnSide = false;   // the current users of the set wait for buildDone (wait_bvh)
@@ -279,6 +286,7 @@ struct rt_context {
     uint32_t bvhSkipPublish = 0xFFFFFFFFu;
     int bvhSkipBuilds = -1;  // [debug] bvhSkipPublishBuilds: the fault applies to this many builds (-1: all)
     float bvhWaitMs = 1000.0f;
+    bool sdfOn = false;      // [render] signedDistance / rt_set_signed_distance: builds write a pseudo-normal table
     int closestStack = 32;   // [debug] closestStack: stack entries of a closest-point query's lanes (2..kClosestStackMax)
     uint32_t buildSeq = 0;   // LBVH builds issued so far (a timeout report names the build)
     // [tuning] scheduling knobs (A/B aids, config only; the defaults are the measured best,
@@ -556,6 +564,7 @@ int build_bvh(rt_context* ctx, int set, hipStream_t stream);  // context.cpp: th
 bool closest_distance_ok(float max_distance);  // closest.cpp
 extern "C" int wait_bvh(rt_context* ctx);  // context.cpp: context stream waits for the LBVH build
 extern "C" int ensure_emitter_lists(rt_context* ctx);  // context.cpp: the existing LBVH sets' emitter-list buffers
+extern "C" int ensure_sdf_tables(rt_context* ctx);  // context.cpp: the existing LBVH sets' pseudo-normal tables
 inline bool emitter_active(const rt_context* ctx) { return ctx->emitterOn && ctx->matCustom && ctx->matEmits; }
 extern "C" int ensure_geometry_motion(rt_context* ctx);  // context.cpp: dPrevVerts and the existing LBVH sets' triDisp
 const char* skin_shape_fault(const rt_skin* s);  // skin.cpp: what is wrong with a skin's pointers or counts, or null

@@ -1553,6 +1553,7 @@ int ensure_bvh_pair(rt_context* ctx) {
     RT_TRY(alloc_bvh_set(ctx, ctx->bvh[1]));
     if (ctx->geomMotion) RT_TRY(ensure_geometry_motion(ctx));  // else with rt_set_geometry_motion
     if (ctx->emitterOn) RT_TRY(ensure_emitter_lists(ctx));     // else with rt_set_emitter_sampling
+    if (ctx->sdfOn) RT_TRY(ensure_sdf_tables(ctx));            // else with rt_set_signed_distance
     // lowest priority: it should fill what the trace chain leaves idle
     if (!ctx->sideStream) RT_TRY(rt_create_stream(ctx, &ctx->sideStream, false));
     for (BvhBufs& b : ctx->bvh) RT_TRY(rt_event(ctx, b.buildDone));
@@ -1998,6 +1999,25 @@ static const char* closest_query_fault(const rt_closest_query* q) {
     return nullptr;
 }
 
+// the descent of a query with n > 0 on LBVH set b, enqueued on s
+static int enqueue_closest(rt_context* ctx, const rt_closest_query* q, const BvhBufs& b, hipStream_t s) {
+    ClosestParams p;
+    p.nodes = b.nodes;
+    p.tlasNodes = b.tlasNodes;
+    p.triPos = b.triPos;
+    p.reorder = b.reorder;
+    p.triCount = b.triCount;
+    p.batchCount = b.B;
+    p.points = q->points;
+    p.stride = q->stride;
+    p.n = q->n;
+    p.limit = q->max_distance * q->max_distance;  // fp32 (-ffp-contract=off): closest_limit
+    p.stackCap = (uint32_t)ctx->closestStack;
+    p.out = q->out;
+    HIP_TRY(ctx, rtk_launch_closest_points(&p, s));
+    return RT_OK;
+}
+
 int rt_closest_points_device(rt_context* ctx, const rt_closest_query* q) {
     if (!ctx || !q) return RT_ERR_ARG;
     if (const char* bad = closest_query_fault(q)) { ctx->err = std::string("rt_closest_points_device: ") + bad; return RT_ERR_ARG; }
@@ -2008,22 +2028,54 @@ int rt_closest_points_device(rt_context* ctx, const rt_closest_query* q) {
         if (int rc = wait_bvh(ctx)) return rc;  // the current set's build, wherever it ran
         BvhBufs& b = ctx->lbvh();
         if (b.B == 0u || b.triCount == 0u) { ctx->err = "rt_closest_points_device before the first rt_build_bvh"; return RT_ERR_STATE; }
-        ClosestParams p;
-        p.nodes = b.nodes;
-        p.tlasNodes = b.tlasNodes;
-        p.triPos = b.triPos;
-        p.reorder = b.reorder;
-        p.triCount = b.triCount;
-        p.batchCount = b.B;
-        p.points = q->points;
-        p.stride = q->stride;
-        p.n = q->n;
-        p.limit = q->max_distance * q->max_distance;  // fp32 (-ffp-contract=off): closest_limit
-        p.stackCap = (uint32_t)ctx->closestStack;
-        p.out = q->out;
-        HIP_TRY(ctx, rtk_launch_closest_points(&p, s));
+        if (int rc = enqueue_closest(ctx, q, b, s)) return rc;
         if (int rc = hold_query_set(ctx, b, s)) return rc;
     }
     if (q->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)q->done_event, s));
+    return RT_OK;
+}
+
+// Signed distance queries (sdf.hip): rt_closest_points_device's descent, or none
+// (RT_DISTANCE_FROM_RECORDS), and behind it on the context stream the dense sign pass over the records,
+// which reads the pseudo-normal table the current set's build wrote (rt_set_signed_distance).  Everything
+// the closest query leaves alone this leaves alone.  Check order: NULL ctx / q, the closest query's
+// argument checks, the distance query's own, then the init state and the table.
+int rt_signed_distance_device(rt_context* ctx, const rt_distance_query* q) {
+    if (!ctx || !q) return RT_ERR_ARG;
+    const rt_closest_query* c = &q->closest;
+    const char* bad = closest_query_fault(c);
+    if (!bad) {
+        if ((q->flags & ~RT_DISTANCE_FROM_RECORDS) != 0u) bad = "unknown flags";
+        else if (c->n > 0u && !q->signed_out) bad = "signed_out must not be NULL";
+        else if (c->n > 0u && ((uintptr_t)q->signed_out & 15u) != 0) bad = "signed_out must be 16-byte aligned";
+    }
+    if (bad) { ctx->err = std::string("rt_signed_distance_device: ") + bad; return RT_ERR_ARG; }
+    if (!ctx->inited) { ctx->err = "rt_signed_distance_device before rt_init"; return RT_ERR_STATE; }
+    // host state of the current set: its build was issued with or without a table, wherever it runs
+    if (!ctx->lbvh().sdfBuilt) {
+        ctx->err = "rt_signed_distance_device: the current build wrote no pseudo-normal table (rt_set_signed_distance, then a build)";
+        return RT_ERR_STATE;
+    }
+    hipStream_t s = ctx->stream;
+    if (c->n > 0u) {
+        if (c->ready_event) HIP_TRY(ctx, hipStreamWaitEvent(s, (hipEvent_t)c->ready_event, 0));
+        if (int rc = wait_bvh(ctx)) return rc;  // the current set's build and its table, wherever they ran
+        BvhBufs& b = ctx->lbvh();
+        if (b.B == 0u || b.triCount == 0u) { ctx->err = "rt_signed_distance_device before the first rt_build_bvh"; return RT_ERR_STATE; }
+        if (!(q->flags & RT_DISTANCE_FROM_RECORDS))
+            if (int rc = enqueue_closest(ctx, c, b, s)) return rc;
+        SdfSignParams p;
+        p.triPos = b.triPos;
+        p.table = b.sdfTable;
+        p.triCount = b.triCount;
+        p.points = c->points;
+        p.stride = c->stride;
+        p.n = c->n;
+        p.records = c->out;
+        p.out = q->signed_out;
+        HIP_TRY(ctx, rtk_launch_sdf_sign(&p, s));
+        if (int rc = hold_query_set(ctx, b, s)) return rc;  // behind the sign pass: the table is the set's
+    }
+    if (c->done_event) HIP_TRY(ctx, hipEventRecord((hipEvent_t)c->done_event, s));
     return RT_OK;
 }

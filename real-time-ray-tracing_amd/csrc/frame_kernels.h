@@ -429,3 +429,34 @@ struct ClosestParams {
 };
 // grid: ceil(n / 128) workgroups, one thread per point
 extern "C" hipError_t rtk_launch_closest_points(const ClosestParams* p, hipStream_t stream);
+
+// The pseudo-normal table of one LBVH build (sdf.hip, rt_set_signed_distance; sdf_kernels.h is the rule):
+// behind the build on its stream, a triangle pass that stores each corner's record at the corner's CSR
+// slot and a gather pass, one thread per corner, that walks the slots of the corner's vertex
+struct SdfTableParams {
+    const float* vertices;       // [nverts][3] the positions the build gathered
+    const uint32_t* indices;     // [triCountPadded][3]
+    const uint32_t* cornerSlot;  // [triCountPadded * 3] corner -> its place in the vertex -> corner CSR
+    const uint32_t* adjOffsets;  // [nverts + 1] the CSR's offsets
+    uint32_t nverts, triCount, triCountPadded;
+    float4* slotNormal;          // [triCountPadded * 3] scratch: (unit normal, the corner's angle) in CSR order
+    uint2* slotOthers;           // [triCountPadded * 3] scratch: the vertex ids at the triangle's two other corners;
+                                 // both 0xFFFFFFFF: the triangle does not count
+    float4* table;               // [triCount][6] out: vertex 1 2 3, edge 12 23 31; .w = 0
+};
+extern "C" hipError_t rtk_launch_sdf_table(const SdfTableParams* p, hipStream_t stream);
+
+// The sign pass of one signed distance query (sdf.hip, rt_signed_distance_device): one lane per point,
+// from the point, its closest record, the set's triangle records and the set's table to one 16-B quad
+struct SdfSignParams {
+    const float4* triPos;     // the LBVH set's triangle records (64 B each), as ClosestParams
+    const float4* table;      // [triCount][6] the set's pseudo-normals
+    uint32_t triCount;        // of the set's build: a record naming a triangle at or past it is a miss
+    const float* points;      // point i at points + i * stride
+    uint32_t stride;          // in floats, >= 3
+    uint32_t n;               // 1 .. RT_QUERY_MAX_RAYS
+    const float* records;     // [n][8] closest records, 16-byte aligned
+    float* out;               // [n][4], 16-byte aligned
+};
+// grid: ceil(n / 256) workgroups, one thread per point
+extern "C" hipError_t rtk_launch_sdf_sign(const SdfSignParams* p, hipStream_t stream);

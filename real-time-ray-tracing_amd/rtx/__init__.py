@@ -28,7 +28,8 @@ ARR = dict(VERTICES=0, INDICES=1, NORMALS=2, TRI_POS=3, AABBS=4, MORTON=5, REORD
            RGBA8=30, PT_STATS=31, PT_QUEUE=32, PT_Q3_ORIGINS=33, PT_Q3_DIRS=34,
            PT_Q4_ORIGINS=35, PT_Q4_DIRS=36, TEX_ALBEDO_AO=37, TEX_NORMAL_ROUGHNESS=38, TEX_HEIGHT=39, HDR=40,
            BVH_ARENA=41, TRI_MATERIALS=42, ADJ_OFFSETS=43, CORNER_SLOTS=44, TRI_MATERIAL_CENSUS=45,
-           EMITTER_TRIS=46, EMITTER_WEIGHTS=47, EMITTER_CDF=48, PT_Q3_BETA=49, SPEC_STATS=50)
+           EMITTER_TRIS=46, EMITTER_WEIGHTS=47, EMITTER_CDF=48, PT_Q3_BETA=49, SPEC_STATS=50,
+           PSEUDO_NORMALS=51)
 TEX = dict(SOIL_ALBEDO_AO=0, SOIL_NORMAL_ROUGHNESS=1, SOIL_HEIGHT=2)  # MipmapTextureName (texture.h:5-12)
 # rt_buffer_name (Buffer2DName, kernel.cuh:286-315)
 BUF = dict(RENDER_COLOR=0, ACCUMULATION=1, HISTORY_COLOR=2, SCALED_COLOR=3, NORMAL=10, DEPTH=11, HISTORY_DEPTH=12,
@@ -114,6 +115,11 @@ class ClosestQuery(C.Structure):
                 ("out", C.c_void_p), ("ready_event", C.c_void_p), ("done_event", C.c_void_p)]
 
 
+class DistanceQuery(C.Structure):
+    """rt_distance_query: one device signed distance query (rt_signed_distance_device)."""
+    _fields_ = [("closest", ClosestQuery), ("signed_out", C.c_void_p), ("flags", C.c_uint32)]
+
+
 class Mesh(C.Structure):
     """rt_mesh: an indexed mesh for rt_set_mesh / rt_set_mesh_device."""
     _fields_ = [("xyz", C.c_void_p), ("vertex_count", C.c_uint32), ("indices", C.c_void_p),
@@ -181,6 +187,7 @@ SURFACE_FROM_HITS, SURFACE_MOTION = 1, 2  # RT_SURFACE_*
 
 CLOSEST_FLOATS = 8                           # RT_CLOSEST_FLOATS
 CLOSEST_FRONT, CLOSEST_FOUND = 1 << 16, 1 << 17  # RT_CLOSEST_*: bits of a closest-point record's last word
+DISTANCE_FROM_RECORDS = 1                    # RT_DISTANCE_FROM_RECORDS
 
 
 def surface_floats(flags: int) -> int:
@@ -236,6 +243,11 @@ SIGNATURES = {
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.POINTER(ClosestQuery)]),
     "rt_point_triangle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_closest_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "rt_set_signed_distance": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_get_signed_distance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_signed_distance_device": (C.c_int, [C.c_void_p, C.POINTER(DistanceQuery)]),
+    "rt_pseudo_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_signed_distance_rule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rt_array_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "rt_save_camera": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -334,7 +346,7 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
                  geometry_motion: bool | None = None, max_triangles: int | None = None,
                  max_vertices: int | None = None, texture_sets: int | None = None,
                  emitter_sampling: bool | None = None, emitter_probability: float | None = None,
-                 sky_sets: int | None = None) -> str:
+                 sky_sets: int | None = None, signed_distance: bool | None = None) -> str:
     """Write a config.toml with the reference's three tables (resources/config.toml) + extensions.
 
     `tuning`: the [tuning] table (scheduling A/B aids, include/rtx_amd.h).  When None, the
@@ -348,7 +360,9 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
     written, one set).
     `emitter_sampling` / `emitter_probability`: [render] emitterSampling / emitterProbability, the initial
     state of rt_set_emitter_sampling (None: the keys are not written; off, 0.5).
-    `sky_sets`: [scene] skySets, the sky sets the context holds (None: the key is not written, one set)."""
+    `sky_sets`: [scene] skySets, the sky sets the context holds (None: the key is not written, one set).
+    `signed_distance`: [render] signedDistance, the initial state of rt_set_signed_distance (None: the key
+    is not written, the default is off)."""
     with open(path, "w") as f:
         f.write("[resolution]\nwidth = %d\nheight = %d\n\n" % (width, height))
         if camera_file:
@@ -377,6 +391,8 @@ def write_config(path: str, width: int, height: int, dynamic: bool = False, chun
             f.write("emitterSampling = %s\n" % ("true" if emitter_sampling else "false"))
         if emitter_probability is not None:
             f.write("emitterProbability = %r\n" % float(emitter_probability))
+        if signed_distance is not None:
+            f.write("signedDistance = %s\n" % ("true" if signed_distance else "false"))
         f.write(extra)
         if tuning is None:
             tuning = tuning_from_env()
@@ -625,6 +641,20 @@ class RayTracer:
         on, q = C.c_int(), C.c_float()
         self._check(self.lib.rt_get_emitter_sampling(self.h, C.byref(on), C.byref(q)), "rt_get_emitter_sampling")
         return bool(on.value), q.value
+
+    # ---- signed distance queries (rt_set_signed_distance, include/rtx_amd.h)
+    @property
+    def signed_distance(self) -> bool:
+        """Signed distance queries (rt_set_signed_distance): every LBVH build writes its pseudo-normal table,
+        which signed_distance_device reads.  Takes effect from the next build; download("PSEUDO_NORMALS")
+        returns the table of the last build."""
+        v = C.c_int()
+        self._check(self.lib.rt_get_signed_distance(self.h, C.byref(v)), "rt_get_signed_distance")
+        return bool(v.value)
+
+    @signed_distance.setter
+    def signed_distance(self, on: bool):
+        self._check(self.lib.rt_set_signed_distance(self.h, 1 if on else 0), "rt_set_signed_distance")
 
     # ---- per-triangle materials (rt_set_triangle_materials, include/rtx_amd.h)
     def set_triangle_materials(self, ids: np.ndarray, first: int = 0):
@@ -928,7 +958,7 @@ class RayTracer:
                 raise ValueError("download: set applies to TEX_ALBEDO_AO / TEX_NORMAL_ROUGHNESS, as a small positive index")
             what |= int(set) << 8
         n = self.lib.rt_array_bytes(self.h, what)
-        if n == 0 and name.startswith("EMITTER_"):  # an empty emitter list, or none
+        if n == 0 and (name.startswith("EMITTER_") or name == "PSEUDO_NORMALS"):  # an empty emitter list, or none; no table
             return np.empty(0, dtype=dtype)
         buf = np.empty(n, dtype=np.uint8)
         self._check(self.lib.rt_download(self.h, what, buf.ctypes.data, n), "rt_download(%s)" % name)
@@ -997,6 +1027,21 @@ class RayTracer:
                 raise ValueError("closest_points_device: %s must fit 32 bits" % name)
         q = ClosestQuery(points_ptr, int(stride), int(n), float(max_distance), out_ptr, ready_event, done_event)
         self._check(self.lib.rt_closest_points_device(self.h, C.byref(q)), "rt_closest_points_device")
+
+    def signed_distance_device(self, points_ptr: int, n: int, out_ptr: int, signed_ptr: int, *, stride: int = 3,
+                               max_distance: float = float("inf"), from_records: bool = False,
+                               ready_event: int | None = None, done_event: int | None = None):
+        """rt_signed_distance_device: closest_points_device, whose records go to out_ptr, and behind it the
+        sign pass: n quads of float32 at signed_ptr, the nearest feature's pseudo-normal and the distance,
+        negative inside.  from_records: out_ptr holds the records of an earlier query of the same points on
+        the same build, and only the sign pass runs.  Needs signed_distance on since before the current
+        build.  rtx.query.signed_distance is the torch-tensor form."""
+        for name, v in (("n", n), ("stride", stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("signed_distance_device: %s must fit 32 bits" % name)
+        q = DistanceQuery(ClosestQuery(points_ptr, int(stride), int(n), float(max_distance), out_ptr, ready_event, done_event),
+                          signed_ptr, DISTANCE_FROM_RECORDS if from_records else 0)
+        self._check(self.lib.rt_signed_distance_device(self.h, C.byref(q)), "rt_signed_distance_device")
 
     def get_buffer(self, name: str, shape=None, dtype=np.uint8) -> np.ndarray:
         if shape is None:
@@ -1128,6 +1173,51 @@ def closest_points_host(triangles, points, *, ids=None, max_distance: float = fl
                                                float(max_distance), out.ctypes.data if len(p) else None)
     if rc != RT_OK:
         raise RtError("rt_closest_points_host: %s" % ERRORS.get(rc, rc))
+    return out
+
+
+def pseudo_normals(vertices, indices) -> np.ndarray:
+    """rt_pseudo_normals: the pseudo-normal table of a mesh on the host (no context, no device): vertices
+    (nv, 3), indices (ntri, 3).  Returns (ntri, 6, 4) float32: per triangle vertex 1 2 3, edge 12 23 31,
+    .w = 0; bit for bit what download("PSEUDO_NORMALS") gives for a build of the same mesh."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    i = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    out = np.zeros((len(i), 6, 4), np.float32)
+    rc = load_library().rt_pseudo_normals(v.ctypes.data if len(v) else None, len(v), i.ctypes.data if len(i) else None,
+                                          len(i), out.ctypes.data if len(i) else None)
+    if rc != RT_OK:
+        raise RtError("rt_pseudo_normals: %s" % ERRORS.get(rc, rc))
+    return out
+
+
+def signed_distance_rule(points, records, vertices, indices, table) -> np.ndarray:
+    """rt_signed_distance_rule for every point: points (n, 3), their closest records (n, 8), the mesh and
+    its table (pseudo_normals or download("PSEUDO_NORMALS")).  Returns (n, 4) float32: the nearest
+    feature's pseudo-normal and the signed distance (negative inside); a miss gives (0, 0, 0, inf).  A
+    record whose triangle index is not below the table's triangle count is finished as a miss, as the
+    device query does."""
+    p = np.ascontiguousarray(points, np.float32)
+    r = np.ascontiguousarray(records, np.float32)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    t = np.ascontiguousarray(table, np.float32).reshape(-1, 24)
+    if p.ndim != 2 or p.shape[1] != 3 or r.shape != (len(p), 8):
+        raise ValueError("signed_distance_rule: points is (n, 3), records is (n, 8)")
+    if len(t) > len(idx):
+        raise ValueError("signed_distance_rule: the table has more triangles than the mesh")
+    lib = load_library()
+    out = np.zeros((len(p), 4), np.float32)
+    tri = r.view(np.uint32)[:, 4]
+    miss = np.array([0.0, 0.0, 0.0, np.inf], np.float32)
+    for k in range(len(p)):
+        if tri[k] >= len(t):
+            out[k] = miss
+            continue
+        xyz = np.ascontiguousarray(v[idx[tri[k]]]).reshape(9)
+        rc = lib.rt_signed_distance_rule(p[k].ctypes.data, r[k].ctypes.data, xyz.ctypes.data, t[tri[k]].ctypes.data,
+                                         out[k].ctypes.data)
+        if rc != RT_OK:
+            raise RtError("rt_signed_distance_rule: %s" % ERRORS.get(rc, rc))
     return out
 
 

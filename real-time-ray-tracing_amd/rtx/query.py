@@ -17,6 +17,11 @@ the current build and the nearest point on it (rt_closest_points_device), one (n
 (views: ``closest_position`` .. ``closest_found``), for colliders, penetration depth, distance-field
 sampling and placement on skinned meshes.
 
+``signed_distance(rt, points)`` adds "inside or outside" (rt_signed_distance_device): the closest records
+and one (n, 4) quad per point, the nearest feature's angle-weighted pseudo-normal and the distance,
+negative inside a closed mesh (views: ``signed_distance_of``, ``pseudo_normal``, ``inside``).  It needs
+``rt.signed_distance = True`` since before the current build.
+
 The query runs on the renderer's stream (``set_stream``).  ``trace`` may be called from any torch
 stream: it hands the renderer an event recorded on ``torch.cuda.current_stream()`` to wait for, and
 makes that stream wait for the query's end, so tensors filled just before the call are read after
@@ -179,6 +184,54 @@ def closest(rt, points, *, max_distance: float = float("inf"), out=None):
     return rec
 
 
+def signed_distance(rt, points, *, max_distance: float = float("inf"), out=None, signed_out=None, records=None):
+    """Closest-point records and signed distances of the points against the build that is current now.
+
+    points, max_distance, out: as ``closest``.  signed_out: a contiguous (n, 4) float32 tensor for the
+    quads.  records: the contiguous (n, 8) records of an earlier query of the same points on the build
+    that is current now (that it is the same build is the caller's responsibility): nothing descends,
+    only the sign pass runs (RT_DISTANCE_FROM_RECORDS), and they are returned as they are; out must then
+    be None.  The renderer's ``signed_distance`` must have been on since before the current build.
+
+    Returns (records (n, 8), signed (n, 4)): the nearest feature's pseudo-normal, not normalised, and the
+    distance, negative where the point lies behind it; (0, 0, 0, inf) on a miss.  Same event protocol
+    as ``trace``."""
+    import torch
+
+    n, stride = _rays("points", points, torch)
+    if n > (1 << 30):
+        raise ValueError("at most 2^30 points per query")
+    if not max_distance >= 0.0:
+        raise ValueError("max_distance must be >= 0 or inf")
+    if records is not None and out is not None:
+        raise ValueError("records are read in place: out must be None")
+    _dense("out", out, (n, 8), torch)
+    _dense("records", records, (n, 8), torch)
+    _dense("signed_out", signed_out, (n, 4), torch)
+    if not points.is_cuda:
+        raise ValueError("points must be on the renderer's device, not on %s" % points.device)
+    dev = points.device
+    if any(x is not None and x.device != dev for x in (out, records, signed_out)):
+        raise ValueError("points, out, records, signed_out must be on one device")
+    dev_id = rt.info().deviceId
+    if dev_id >= 0 and dev.index is not None and dev.index != dev_id:
+        raise ValueError("the points are on %s, the renderer on device %d" % (dev, dev_id))
+    cur = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        rec = records if records is not None else out
+        if rec is None:
+            rec = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        sd = signed_out if signed_out is not None else torch.empty((n, 4), dtype=torch.float32, device=dev)
+        ready, done = torch.cuda.Event(), torch.cuda.Event()
+        ready.record(cur)
+        done.record(cur)  # creates the handle; the renderer records it again behind the kernels
+        rt.signed_distance_device(points.data_ptr(), n, rec.data_ptr(), sd.data_ptr(), stride=stride,
+                                  max_distance=max_distance, from_records=records is not None,
+                                  ready_event=ready.cuda_event, done_event=done.cuda_event)
+        cur.wait_event(done)
+    return rec, sd
+
+
 def split(hits):
     """(t, tri, u, v) views of an (n, 4) hit tensor; tri is int32, -1 on a miss."""
     return t_of(hits), tri_of(hits), u_of(hits), v_of(hits)
@@ -312,3 +365,22 @@ def closest_front(rec):
 
 def closest_found(rec):
     return (closest_word(rec) & (1 << 17)) != 0
+
+
+# ---- views of an (n, 4) signed distance tensor
+
+
+def signed_distance_of(signed):
+    """The distance to the nearest point of the mesh, negative inside, (n,); inf on a miss."""
+    return signed[:, 3]
+
+
+def pseudo_normal(signed):
+    """The nearest feature's pseudo-normal, (n, 3): a face's unit normal, the sum of an edge's unit normals,
+    a vertex's angle-weighted sum.  Not normalised; all zero on a miss or where no incident triangle counted."""
+    return signed[:, 0:3]
+
+
+def inside(signed):
+    """Whether the point lies inside the closed mesh, bool (n,); False on a miss."""
+    return signed[:, 3] < 0
